@@ -3,7 +3,7 @@
 cutout cross-correlations/sec, 64x64 px cutout pairs, upsample=10, 1e5 pairs per GPU
 resident in HBM, on N MI355X of one node (one process per GPU, weak scaling).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -11,6 +11,11 @@ A "step" is one pass of the hot path (spx_xcorr_refine_f32: FFT cross-correlatio
 arg-max -> MFMA upsampled-DFT refine -> 5x5 quadratic fit) over the rank's whole batch,
 followed -- when N > 1 -- by the RCCL gather of the per-cutout (dx, dy) to rank 0.
 Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps and the line.
+--full adds the measurements that are not the headline (at N = 1): the CPU baseline (`cpu_baseline`)
+and the reference-mode block (`reference_mode`).  --dump-outputs DIR writes the gathered (dx, dy) of
+the last timed step to DIR/shifts.npy (float64 [pairs, 2]; inputs are seeded, so runs compare row by row).
 """
 import argparse
 import json
@@ -272,6 +277,21 @@ def reference_mode_block(dev, steps, warmup):
     }
 
 
+DUMP_MAX_BYTES = 60 * 10 ** 6       # --dump-outputs stays below 64 MB (at 8 GPUs config 4 gathers 160 MB of shifts)
+
+
+def dump_outputs(out_dir, shifts):
+    """Write the timed path's result, `shifts` [n, 2] float64, to out_dir/shifts.npy.  Above DUMP_MAX_BYTES
+    a fixed, seeded sample of its rows (in row order) is written instead."""
+    import numpy as np
+    a = shifts.cpu().numpy().astype(np.float64, copy=False)
+    rows = DUMP_MAX_BYTES // a[0].nbytes
+    if len(a) > rows:
+        a = a[np.sort(np.random.default_rng(20261016).choice(len(a), size=rows, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, 'shifts.npy'), a)
+
+
 def launch_ranks(n, argv):
     """`python bench.py --gpus N` as typed: one child `python -m torch.distributed.run` with N ranks on
     127.0.0.1 (a free port), stdout/stderr passed through.  Returns the child's exit code."""
@@ -294,9 +314,13 @@ def main():
     ap.add_argument('--warmup', type=int, default=10)
     ap.add_argument('--pairs', type=int, default=None,
                     help='pairs per GPU (default 1e5 = configs[1]; at 8 GPUs 1.25e6 = configs[3], 1e7 pairs in all)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also run what the headline does not need (N=1): the CPU baseline and the reference-mode block')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the last timed step's gathered (dx, dy) to DIR/shifts.npy (float64)")
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--no-reference-mode', action='store_true',
-                    help='skip the reference-mode (cc.find_displacement) block of the N=1 line')
+                    help='with --full: skip the reference-mode (cc.find_displacement) block of the N=1 line')
     ap.add_argument('--tile', type=int, default=TILE, help='cutout side (64 = config 2, 128 = config 3)')
     ap.add_argument('--upsample', type=int, default=UPSAMPLE)
     ap.add_argument('--refine', default='default', choices=['default', 'float64', 'float32'],
@@ -305,6 +329,8 @@ def main():
     ap.add_argument('--backend', default='nccl', help="'gloo' + --one-device rehearses the N>1 path on one GPU")
     ap.add_argument('--one-device', action='store_true', help='every rank uses cuda:0 (rehearsal only)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         # plain `python bench.py --gpus N`: start the N ranks as CHILD processes (one per GPU, the same
@@ -319,7 +345,7 @@ def main():
 
     # CPU baseline first (fork pool), before this process touches the GPU
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.tile, args.upsample)
 
     import torch
@@ -367,13 +393,17 @@ def main():
         if world > 1:
             dist.barrier()
 
+    def check(d):
+        # sanity: the thing being timed is the correct answer
+        err = float((d - truth).abs().max())
+        # (n = 32 spots are clipped by the tile, which biases the truth comparison itself)
+        assert err < (1e-3 if tile > 32 else 1e-2), "shifts are wrong (%g px): refusing to time" % err
+        return err
+
     for _ in range(args.warmup):
         d, g = step()
     torch.cuda.synchronize()
-    # sanity: the thing being timed is the correct answer
-    err = float((d - truth).abs().max())
-    # (n = 32 spots are clipped by the tile, which biases the truth comparison itself)
-    assert err < (1e-3 if tile > 32 else 1e-2), "shifts are wrong (%g px): refusing to time" % err
+    err = check(d) if args.warmup else None
 
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
           for _ in range(args.steps)]
@@ -390,7 +420,7 @@ def main():
         if pending is not None:
             pending.result()
         pending = gather(d, async_op=True)
-    pending.result()
+    shifts = pending.result()             # the last step's (dx, dy) of every rank, on rank 0
     torch.cuda.synchronize()
     barrier()
     elapsed = time.perf_counter() - t0
@@ -399,8 +429,12 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     kern_ms = sum(a.elapsed_time(b) for a, b in ev) / args.steps
+    if err is None:                       # no warm-up step: check the last timed one
+        err = check(d)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, shifts)
     refmode = None
-    if rank == 0 and world == 1 and not args.no_reference_mode and tile == TILE:
+    if args.full and rank == 0 and world == 1 and not args.no_reference_mode and tile == TILE:
         del ref, img
         refmode = reference_mode_block(dev, max(3, args.steps // 5), 2)
 

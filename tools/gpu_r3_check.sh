@@ -6,7 +6,7 @@ O=gpurun_out/r03
 timeout -k 10 1500 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.log 2>&1; rc=$?
 tail -4 $O/pytest_gpu.log
 [ $rc -eq 0 ] || exit 1
-python bench.py --no-cpu-baseline > $O/bench_64.json 2>/dev/null || exit 1
+python bench.py --full --no-cpu-baseline > $O/bench_64.json 2>/dev/null || exit 1
 python - <<'PY'
 import json
 d = json.load(open('gpurun_out/r03/bench_64.json'))

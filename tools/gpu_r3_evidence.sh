@@ -2,11 +2,12 @@
 # Round-3 evidence pass on the shipped library (run LAST: the traffic / FLOP files carry the kernel-source fingerprint).
 # Writes gpurun_out/r03e/...; copy to profiles/r03/ afterwards (tools/collect_r03.sh).
 set -o pipefail
+R=$(cd "$(dirname "$0")/.." && pwd)
 O=$GRAFT_REPO_ROOT/gpurun_out/r03e
 mkdir -p $O
 export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
-B="python3 $GRAFT_REPO_ROOT/bench.py"
+B="python3 $R/bench.py --full"
 step() { echo "== $1"; }
 step "bench (default flags)"; $B > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
 step "kernel trace"; cd /tmp

@@ -2,10 +2,11 @@
 # SQ counter passes of the bench command WITH its reference-mode block (tools/gpu_sq.sh switches that block off), reduced
 # for the five-transform reference-mode kernel spx::p5::disp5p_kernel (20000 sources of 64x64 per launch, NCC).
 set -o pipefail
+R=$(cd "$(dirname "$0")/.." && pwd)
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 cd /tmp
-B="python3 $GRAFT_REPO_ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline"
+B="python3 $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline"
 run() { local name=$1; shift
   timeout -k 10 600 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $GRAFT_REPO_ROOT/gpurun_out/pmc_${name}_ref -- $B > $GRAFT_REPO_ROOT/gpurun_out/pmc_${name}_ref.log 2>&1 || { tail -5 $GRAFT_REPO_ROOT/gpurun_out/pmc_${name}_ref.log; return 1; }
 }

@@ -46,7 +46,7 @@ def main():
     ap.add_argument('--pairs', type=int, default=100000); ap.add_argument('--sources', type=int, default=0)
     a = ap.parse_args()
     pat = 'pair32_kernel' if a.tile <= 32 else ('pair128_kernel' if a.tile > 85 else 'pair_kernel')
-    cmd = 'rocprofv3 --pmc <COUNTER> --kernel-trace --output-format csv -- python3 bench.py --steps 3 --warmup 1 ' \
+    cmd = 'rocprofv3 --pmc <COUNTER> --kernel-trace --output-format csv -- python3 bench.py --full --steps 3 --warmup 1 ' \
           '--no-cpu-baseline --tile %d --upsample %d (one pass per counter, tools/gpu_r3_evidence.sh)' % (a.tile, a.upsample)
     r = reduce(a.fetch_dir, a.write_dir, pat, a.pairs, 2 * a.tile * a.tile * 4 + 20, 'pairs_per_launch',
                {'tile': a.tile, 'upsample': a.upsample, 'command': cmd})

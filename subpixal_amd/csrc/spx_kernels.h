@@ -1300,6 +1300,7 @@ struct RefineF32 {
     typedef float S;
     typedef f32x4 V4;
     static constexpr int kPreloadMax = 2;        // window blocks whose tables are held in registers
+    static constexpr bool kRolled = true;        // fine_window_rolled (fixed plane order, rolled tables)
     static SPX_DEVICE V4 zero() { return V4{0.f, 0.f, 0.f, 0.f}; }
     static SPX_DEVICE V4 mma(S a, S b, V4 c) { return rt::mfma_16x16x4(a, b, c); }
     static SPX_DEVICE int drow(int lk, int r) { return 4 * lk + r; }
@@ -1308,6 +1309,7 @@ struct RefineF64 {
     typedef double S;
     typedef rt::f64x4 V4;
     static constexpr int kPreloadMax = 1;        // 16 doubles per table slice: 64 registers for one block
+    static constexpr bool kRolled = false;       // fine_window (operands read rolled by the peak)
     static SPX_DEVICE V4 zero() { return V4{0.0, 0.0, 0.0, 0.0}; }
     static SPX_DEVICE V4 mma(S a, S b, V4 c) { return rt::mfma_f64_16x16x4(a, b, c); }
     static SPX_DEVICE int drow(int lk, int r) { return lk + 4 * r; }
@@ -1448,6 +1450,132 @@ SPX_DEVICE void fine_window(unsigned char* lds, const FineTables<WB, R>& ft,
                     f[bb][ab] = R::mma(sgn * ka[bb][r], acc[ab][t][r], f[bb][ab]);
         }
     }
+    if constexpr (L::fb_count(W) == C * C) {
+#pragma unroll
+        for (int bb = 0; bb < WB; ++bb)
+#pragma unroll
+            for (int ab = 0; ab < WB; ++ab) put(bb, ab, f[bb][ab], 0);
+        rt::block_sync_lds();
+    } else {
+        for (int c = 0; c < C * C; ++c) {
+            if (wave == c) {
+#pragma unroll
+                for (int bb = 0; bb < WB; ++bb)
+#pragma unroll
+                    for (int ab = 0; ab < WB; ++ab) put(bb, ab, f[bb][ab], c);
+            }
+            rt::block_sync_lds();
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Float32 refine on a fixed plane order (RefineF32::kRolled).  K_c(t - m) depends only on m - l_c, so the
+// contraction runs over plane rows / columns in storage order and the roll by the coarse peak sits in the
+// kernel tables instead of the plane reads: the A fragments are peak-independent and are read right after
+// the plane-write barrier, their LDS latency hidden behind the coarse arg-max, and a re-centred window only
+// reloads the tables.
+//   stage 1, step s, lane group lk: plane row r = 4 s + lk, columns 16 t + lj (t = 0..3)
+//   stage 2, tile t, register r:    plane column 16 t + 4 lk + r
+// A plane row r stands for the convolution index m = r (mod 64) in [d0, d0 + 64), d0 = l_c - 32, i.e. table
+// offset m - d0 = (r - d0) mod 64 = (u mod 64) for u = r - (d0 mod 64) + 64 in [1, 128), with the sign of the
+// odd class at m >= 64 (mod 128) = (d0 >> 6) XOR (u < 64): make_ktab's rolled section holds both signs (`flip`).
+// ---------------------------------------------------------------------------
+template <int C>
+SPX_DEVICE void load_afrag(const unsigned char* lds, float (&afrag)[16][4], int rot) {
+    typedef Lds<C> L;
+    const int tid = fresh_tid();
+    const int wave = ((tid >> 6) + rot) & (C * C - 1), lane = tid & 63;     // class, see cc_planes
+    const int lk = lane >> 4, lj = lane & 15;
+    const float* plane = reinterpret_cast<const float*>(lds + L::R_OFF + wave * L::PLANE_STRIDE_BYTES);
+#pragma unroll
+    for (int step = 0; step < 16; ++step) {
+        const int row = 4 * step + lk;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) afrag[step][t] = plane[row * L::PS + plane_col(row, 16 * t + lj)];
+    }
+}
+
+template <int WB> struct RolledTables {
+    float y[WB][16];      // stage 1 B operand of step s
+    float x[WB][16];      // stage 2 A operand of (tile t, register r): [4 t + r]
+};
+// 16 loads per block and axis, one address register each (the step is an immediate offset); the y
+// table first, so that stage 1 waits for it alone
+template <int C, int WB>
+SPX_DEVICE void load_rolled_tables(RolledTables<WB>& rt_, const float* __restrict__ ktab, int ny, int nx,
+                                   int qyc, int qxc, int rot) {
+    const int tid = fresh_tid();
+    const int wave = ((tid >> 6) + rot) & (C * C - 1), lane = tid & 63;     // class, see cc_planes
+    const int cy = wave / C, cx = wave % C;
+    const int lk = lane >> 4, lj = lane & 15;
+    constexpr int kBlk = 128 * 16;          // floats per (class, flip, block)
+    const float* sec = rt::launder(ktab) + 2 * 2 * WB * 64 * 16;     // spx_tables.h ktab_rolled_offset
+    const int dy = conv_index(ny, qyc) - 32, dx = conv_index(nx, qxc) - 32;
+    const float* ty = sec + (cy * 2 + ((dy >> 6) & 1)) * WB * kBlk + (lk - (dy & 63) + 64) * 16 + lj;
+    const float* tx = sec + (cx * 2 + ((dx >> 6) & 1)) * WB * kBlk + (4 * lk - (dx & 63) + 64) * 16 + lj;
+#pragma unroll
+    for (int b = 0; b < WB; ++b)
+#pragma unroll
+        for (int step = 0; step < 16; ++step) rt_.y[b][step] = ty[b * kBlk + 64 * step];
+#pragma unroll
+    for (int b = 0; b < WB; ++b)
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) rt_.x[b][4 * t + r] = tx[b * kBlk + 16 * (16 * t + r)];
+}
+
+template <int C, int WB>
+SPX_DEVICE void fine_window_rolled(unsigned char* lds, const float (&afrag)[16][4], const RolledTables<WB>& kt,
+                                   int rot) {
+    typedef Lds<C> L;
+    typedef RefineF32 R;
+    typedef R::V4 V4;
+    static_assert(C == 2, "");
+    constexpr int W = 16 * WB;
+    const int tid = fresh_tid();
+    const int wave = ((tid >> 6) + rot) & (C * C - 1), lane = tid & 63;     // class, see cc_planes
+    const int lk = lane >> 4, lj = lane & 15;
+    float* fbuf = reinterpret_cast<float*>(lds + L::FB_OFF);
+
+    // stage 1: G^T[col][a] = sum_row plane[row][col] K_y[row][a]
+    V4 acc[WB][4];
+#pragma unroll
+    for (int ab = 0; ab < WB; ++ab)
+#pragma unroll
+        for (int t = 0; t < 4; ++t) acc[ab][t] = R::zero();
+#pragma unroll
+    for (int step = 0; step < 16; ++step)
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int ab = 0; ab < WB; ++ab) acc[ab][t] = R::mma(afrag[step][t], kt.y[ab][step], acc[ab][t]);
+    // stage 2: F^T[b][a] = sum_col K_x[b][col] G^T[col][a]; register r of tile t is column 16 t + 4 lk + r
+    const float scale = 0.5f / (float)(L::P * L::P);
+    V4 f[WB][WB];
+#pragma unroll
+    for (int bb = 0; bb < WB; ++bb)
+#pragma unroll
+        for (int ab = 0; ab < WB; ++ab) f[bb][ab] = R::zero();
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int bb = 0; bb < WB; ++bb)
+#pragma unroll
+                for (int ab = 0; ab < WB; ++ab) f[bb][ab] = R::mma(kt.x[bb][4 * t + r], acc[ab][t][r], f[bb][ab]);
+    // as fine_window: one window per class (W = 16), or one shared window the classes add to in class order
+    auto put = [&](int bb, int ab, const V4& fv, int c) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int b = bb * 16 + R::drow(lk, r), a = ab * 16 + lj;
+            const float val = fv[r] * scale;
+            if constexpr (L::fb_count(W) == C * C) fbuf[wave * W * W + b * W + a] = val;
+            else { if (c == 0) fbuf[b * W + a] = val; else fbuf[b * W + a] += val; }
+        }
+    };
     if constexpr (L::fb_count(W) == C * C) {
 #pragma unroll
         for (int bb = 0; bb < WB; ++bb)
@@ -1644,11 +1772,19 @@ SPX_DEVICE void pair_body(const TIn* __restrict__ ref, const TIn* __restrict__ i
     // the refine stage's constant operands: issue the loads now, use them after the arg-max -- and BEFORE the
     // warm-up below: vmcnt counts in issue order, so a wait for the tables must not include the warm-up's
     // trip to HBM (+1.3 %, profiles/r03/variants_*.txt)
+    // (float32 refine: the peak-independent A fragments of fine_window_rolled instead, read from this wave's own
+    // class plane now so that their latency hides behind the arg-max; its tables follow the arg-max)
+    // (one window block, upsample up to 11.  Two blocks were built the same way and left: the fixed order changes the
+    // float32 accumulation order of the two 64-term chains, which moved sigma 11..15 px spots at upsample 27 from
+    // inside to 1.13e-3 px of the float64 definition (test_gpu_r3.py); four blocks spilled 28 registers)
+    constexpr bool kRolled = WB == 1 && R::kRolled;
     FineTables<(WB > 0 ? WB : 1), R> ft;
-    if constexpr (WB > 0) load_fine_tables<C, WB, R>(ft, ktab, rot);
+    float afrag[kRolled ? 16 : 1][4];
+    if constexpr (kRolled) load_afrag<C>(lds, afrag, rot);
+    else if constexpr (WB > 0) load_fine_tables<C, WB, R>(ft, ktab, rot);
     // pull the next pair into L2 while this one is in its tail (issuing it before the transforms instead
-    // was measured 2 % slower)
-    if constexpr (sizeof(TIn) == 4) if (next_ref) warm = warm_next_pair(next_ref, next_img);
+    // was measured 2 % slower); the rolled path issues it behind its tables, see below
+    if constexpr (sizeof(TIn) == 4 && !kRolled) if (next_ref) warm = warm_next_pair(next_ref, next_img);
 
     // coarse arg-max over the flipped 'same' window (centroid.py:114-116)
     float bv;
@@ -1678,7 +1814,15 @@ SPX_DEVICE void pair_body(const TIn* __restrict__ ref, const TIn* __restrict__ i
         int imax = 0, jmax = 0;
         bool inside = false;
         for (int iter = 0; iter < 4; ++iter) {
-            fine_window<C, (WB > 0 ? WB : 1), R>(lds, ft, ny, nx, qyc, qxc, rot);
+            if constexpr (kRolled) {
+                RolledTables<(WB > 0 ? WB : 1)> kt;
+                load_rolled_tables<C, (WB > 0 ? WB : 1)>(kt, ktab, ny, nx, qyc, qxc, rot);
+                // after the tables: vmcnt counts in issue order, and the refine must not wait for a trip to HBM
+                if constexpr (sizeof(TIn) == 4) if (iter == 0 && next_ref) warm = warm_next_pair(next_ref, next_img);
+                fine_window_rolled<C, (WB > 0 ? WB : 1)>(lds, afrag, kt, rot);
+            } else {
+                fine_window<C, (WB > 0 ? WB : 1), R>(lds, ft, ny, nx, qyc, qxc, rot);
+            }
             clk.tick(12);
             if constexpr (DBG == 12) { if (tid == 0) out[0] = (double)fine_value<C, W>(lds, 0, 0); return; }
             // arg-max over the part of the window inside the virtual image: every wave scans

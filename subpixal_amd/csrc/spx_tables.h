@@ -46,13 +46,28 @@ inline double class_kernel(int c, int P, double t) {
     return s / (double)(P / 2);
 }
 
-// Lane-major operand tables of the MFMA fine-window stage (spx_kernels.h
-// fine_window), W = 16*blocks, lane = 16 lk + lj:
+// Lane-major operand tables of the MFMA fine-window stage (spx_kernels.h fine_window,
+// spx_kernels8.h fine_window8), W = 16*blocks, lane = 16 lk + lj:
 //   [0][c][blk][lane][s]      = K_c( -(16 blk + lj - W/2)/U - (4 s + lk - 32) )
 //   [1][c][blk][lane][4 t + r] = K_c( -(16 blk + lj - W/2)/U - (16 t + 4 lk + r - 32) )
+// followed by the rolled tables of the four-wave kernel's float32 refine on one window block
+// (spx_kernels.h load_rolled_tables), rows u in [0, 128) of 16 consecutive window offsets a:
+//   [c][flip][blk][u][a] = sgn K_c( -(16 blk + a - W/2)/U - ((u mod 64) - 32) ),
+//   sgn = -1 for c = 1 and flip != (u < 64), else +1
+inline size_t ktab_rolled_offset(int W) { return (size_t)2 * 2 * (W / 16) * 64 * 16; }
 inline std::vector<float> make_ktab(int P, int U, int W) {
     const int blocks = W / 16;
-    std::vector<float> k((size_t)2 * 2 * blocks * 64 * 16);
+    std::vector<float> k(ktab_rolled_offset(W) + (size_t)2 * 2 * blocks * 128 * 16);
+    for (int c = 0; c < 2; ++c)
+        for (int flip = 0; flip < 2; ++flip)
+            for (int blk = 0; blk < blocks; ++blk)
+                for (int u = 0; u < 128; ++u)
+                    for (int a = 0; a < 16; ++a) {
+                        const double t = -(double)(16 * blk + a - W / 2) / (double)U - (double)((u & 63) - 32);
+                        const double sgn = (c == 1 && flip != (u < 64)) ? -1.0 : 1.0;
+                        k[ktab_rolled_offset(W) + ((((size_t)c * 2 + flip) * blocks + blk) * 128 + u) * 16 + a] =
+                            (float)(sgn * class_kernel(c, P, t));
+                    }
     for (int which = 0; which < 2; ++which)
         for (int c = 0; c < 2; ++c)
             for (int blk = 0; blk < blocks; ++blk)

@@ -20,7 +20,7 @@
  *                                   + find_peak, cc.py:86, on a U-times finer grid).
  *   spx_find_peak_f64           <-  centroid.find_peak(image, xmax, ymax, peak_fit_box,
  *                                   peak_search_box, mask)        subpixal/centroid.py:18-236.
- *   spx_gather_cutouts_f32      <-  Cutout.__init__ slicing/fill  subpixal/cutout.py:737-755
+ *   spx_gather_cutouts_f32/_f64 <-  Cutout.__init__ slicing/fill  subpixal/cutout.py:737-755
  *                                   + masked-pixel zeroing        subpixal/align.py:661.
  *   spx_label_bboxes_i32        <-  per-source bounding boxes from the segmentation image
  *                                   subpixal/cutout.py:151-160 (one pass for all sources).
@@ -278,6 +278,11 @@ int spx_find_peak_f64(const double* image, const uint8_t* mask, const double* gu
 int spx_gather_cutouts_f32(const float* frame, const uint8_t* fmask, int fny, int fnx,
                            const int32_t* boxes, int64_t nbatch, int tny, int tnx, float fill,
                            float* tiles, const int32_t* seg, const int32_t* ids, void* stream);
+/* The same for a float64 frame: frame, fill and tiles are float64 (the reference's Cutout keeps the data's
+ * dtype, cutout.py:698-701); everything else as spx_gather_cutouts_f32. */
+int spx_gather_cutouts_f64(const double* frame, const uint8_t* fmask, int fny, int fnx,
+                           const int32_t* boxes, int64_t nbatch, int tny, int tnx, double fill,
+                           double* tiles, const int32_t* seg, const int32_t* ids, void* stream);
 
 /*
  * Bounding boxes of every segment of a label image in one pass (replaces the per-source
@@ -326,7 +331,8 @@ int spx_blot_poly4_f32(const float* src, int64_t nbatch, int sny, int snx, const
  * over sources or pixels.  Packed layout shared by the three calls: item p's (h x w) pixels, row-major, at
  * element item_offset[p] of a flat float32 buffer; its four dithered blots at 4 * item_offset[p]
  * (order 00, 10, 01, 11); its interlaced image (2h x 2w) at 4 * item_offset[p] of `out_icc`;
- * item_shape = int32 [nbatch][2] = (h, w).
+ * item_shape = int32 [nbatch][2] = (h, w).  Each call has a float64 sibling (`_f64`, the blots
+ * `_to_f64`) for catalogs of float64 frames: the reference computes in the cutouts' dtype.
  */
 
 /* frame -> packed cutouts (cutout.py:689-797 slicing/fill + align.py:661 zeroing; see spx_gather_cutouts_f32
@@ -334,6 +340,11 @@ int spx_blot_poly4_f32(const float* src, int64_t nbatch, int sny, int snx, const
 int spx_gather_cutouts_var_f32(const float* frame, const uint8_t* fmask, int fny, int fnx,
                                const int32_t* boxes, int64_t nbatch, const int64_t* item_offset,
                                float fill, float* packed, const int32_t* seg, const int32_t* ids,
+                               void* stream);
+/* ... for a float64 frame: frame, fill and packed are float64 (the packed layout of the float64 catalog) */
+int spx_gather_cutouts_var_f64(const double* frame, const uint8_t* fmask, int fny, int fnx,
+                               const int32_t* boxes, int64_t nbatch, const int64_t* item_offset,
+                               double fill, double* packed, const int32_t* seg, const int32_t* ids,
                                void* stream);
 
 /* packed drizzled cutouts -> packed blots (the four blot_cutout calls of align.py:664-676 per source).
@@ -344,6 +355,12 @@ int spx_gather_cutouts_var_f32(const float* frame, const uint8_t* fmask, int fny
 int spx_blot4_var_f32(const float* src, const int64_t* src_offset, const int32_t* src_shape,
                       int64_t nbatch, const double* map, int degree, const float* gain,
                       const int64_t* dst_offset, const int32_t* dst_shape, float* im4, void* stream);
+/* ... with the blots stored as float64, for float64 image cutouts (blot.py:155 writes tblot's float32
+ * result into a copy of the image cutout): src, the resampling and gain stay float32 (blot.py:134), so each
+ * value is spx_blot4_var_f32's, widened exactly. */
+int spx_blot4_var_to_f64(const float* src, const int64_t* src_offset, const int32_t* src_shape,
+                         int64_t nbatch, const double* map, int degree, const float* gain,
+                         const int64_t* dst_offset, const int32_t* dst_shape, double* im4, void* stream);
 
 /* cc.find_displacement for every item of a packed catalog: ONE call launches each kernel family named in
  * `family_mask` (bit 0: larger side 3..32 px, bit 1: 33..64, bit 2: 65..85, bit 3: 86..128) over the same
@@ -356,6 +373,13 @@ int spx_blot4_var_f32(const float* src, const int64_t* src_offset, const int32_t
 #define SPX_FAMILY_85 4
 #define SPX_FAMILY_128 8
 int spx_find_displacement5_catalog_f32(const float* ref, const float* im4, const int64_t* item_offset,
+                                       const int32_t* item_shape, int64_t nbatch, int family_mask,
+                                       int cc_type, double* out_dxdy, int32_t* out_status,
+                                       float* out_icc, void* workspace, size_t workspace_bytes,
+                                       void* stream);
+/* ... for float64 cutouts and blots (the packed float64 catalog): masks, statistics and normalisation in
+ * float64 before the float32 transforms, as spx_find_displacement5_f64; out_icc stays float32. */
+int spx_find_displacement5_catalog_f64(const double* ref, const double* im4, const int64_t* item_offset,
                                        const int32_t* item_shape, int64_t nbatch, int family_mask,
                                        int cc_type, double* out_dxdy, int32_t* out_status,
                                        float* out_icc, void* workspace, size_t workspace_bytes,

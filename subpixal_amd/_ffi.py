@@ -51,13 +51,22 @@ _SIGNATURES = {
                                                   _vp, _vp, _c.c_size_t, _vp]),
     'spx_find_displacement5_catalog_f32': (_c.c_int, [_vp, _vp, _vp, _vp, _c.c_int64, _c.c_int, _c.c_int, _vp, _vp,
                                                       _vp, _vp, _c.c_size_t, _vp]),
+    # ... for float64 cutouts and blots (out_icc stays float32)
+    'spx_find_displacement5_catalog_f64': (_c.c_int, [_vp, _vp, _vp, _vp, _c.c_int64, _c.c_int, _c.c_int, _vp, _vp,
+                                                      _vp, _vp, _c.c_size_t, _vp]),
     'spx_gather_cutouts_var_f32': (_c.c_int, [_vp, _vp, _c.c_int, _c.c_int, _vp, _c.c_int64, _vp, _c.c_float,
                                               _vp, _vp, _vp, _vp]),
+    'spx_gather_cutouts_var_f64': (_c.c_int, [_vp, _vp, _c.c_int, _c.c_int, _vp, _c.c_int64, _vp, _c.c_double,
+                                              _vp, _vp, _vp, _vp]),
     'spx_blot4_var_f32': (_c.c_int, [_vp, _vp, _vp, _c.c_int64, _vp, _c.c_int, _vp, _vp, _vp, _vp, _vp]),
+    # ... the same float32 blots stored as float64 (for float64 image cutouts)
+    'spx_blot4_var_to_f64': (_c.c_int, [_vp, _vp, _vp, _c.c_int64, _vp, _c.c_int, _vp, _vp, _vp, _vp, _vp]),
     'spx_find_peak_f64': (_c.c_int, [_vp, _vp, _vp, _c.c_int64, _c.c_int, _c.c_int, _c.c_int,
                                      _c.c_int, _c.c_int, _c.c_int, _vp, _vp, _vp]),
     'spx_gather_cutouts_f32': (_c.c_int, [_vp, _vp, _c.c_int, _c.c_int, _vp, _c.c_int64,
                                           _c.c_int, _c.c_int, _c.c_float, _vp, _vp, _vp, _vp]),
+    'spx_gather_cutouts_f64': (_c.c_int, [_vp, _vp, _c.c_int, _c.c_int, _vp, _c.c_int64,
+                                          _c.c_int, _c.c_int, _c.c_double, _vp, _vp, _vp, _vp]),
     'spx_label_bboxes_i32': (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int32, _vp, _vp, _vp]),
     'spx_blot_affine4_f32': (_c.c_int, [_vp, _c.c_int64, _c.c_int, _c.c_int, _vp, _vp, _c.c_int,
                                         _c.c_int, _vp, _vp]),

@@ -238,7 +238,11 @@ def _find_linear_fit_catalog(img_cat, drz_cat, wcslin, fitgeom, nclip, sigma, us
     catalog -- gather of the variable-shape cutouts from the resident frames, masked pixels of the drizzled
     cutouts zeroed (align.py:661), the four blots per source, ``cc.find_displacement`` -- with no host loop
     over sources; only the (dx, dy) and status arrays come back for the fit.  Per source the arithmetic is that
-    of the list path, so the shifts are bit-identical to calling ``cc.find_displacement`` source by source."""
+    of the list path, so the shifts are bit-identical to calling ``cc.find_displacement`` source by source.
+
+    The computation dtype is the image catalog's, as in the reference: the blots take the image cutouts' dtype
+    (blot.py:155) and ``cc.find_displacement`` works in it (cc.py:121-156).  The drizzled cutouts are zeroed in
+    their own catalog's dtype and resampled in float32 (align.py:661, then blot.py:134)."""
     import torch
     from . import blot as _blot
     from .cutout import CutoutCatalog, PackedImages
@@ -262,14 +266,17 @@ def _find_linear_fit_catalog(img_cat, drz_cat, wcslin, fitgeom, nclip, sigma, us
 
     img_p, img_off, img_shp = img_cat.packed(zero_masked=False)
     drz_p, drz_off, drz_shp = drz_cat.packed(zero_masked=True)             # align.py:661
+    drz_p = drz_p.to(torch.float32)                                        # tblot's input (blot.py:134)
     shapes = img_cat.shapes
     total = int((shapes[:, 0].astype(np.int64) * shapes[:, 1]).sum())
-    im4 = _blot.blot4_packed(drz_p, drz_off, drz_shp, maps, img_off, img_shp, total, degree, gain)
+    im4 = _blot.blot4_packed(drz_p, drz_off, drz_shp, maps, img_off, img_shp, total, degree, gain,
+                             out_dtype=img_p.dtype)                        # blot.py:155: the image cutout's dtype
     d, st, icc = cc.find_displacement_packed(img_p, im4, img_off, img_shp, shapes, cc_type=cc_type)
     offs_host = np.zeros(npts, dtype=np.int64)
     if npts > 1:
         np.cumsum((shapes[:-1, 0].astype(np.int64) * shapes[:-1, 1]), out=offs_host[1:])
-    # cutouts above 128 px (general path): one launch per shape, from the packed buffers (rare)
+    # cutouts above 128 px (general path): one launch per shape, from the packed buffers (rare); it takes the
+    # float64 entry for a float64 catalog, as find_displacement_packed does
     side, low = shapes.max(axis=1), shapes.min(axis=1)
     for shp in {tuple(x) for x in shapes[(side > 128) & (side <= _ffi.MAX_SIDE) & (low >= 3)]}:
         idx = np.nonzero((shapes == np.array(shp)).all(axis=1))[0]
@@ -297,7 +304,7 @@ def _find_linear_fit_catalog(img_cat, drz_cat, wcslin, fitgeom, nclip, sigma, us
     xyref = frame_xy(img_cat.src_pos[:, 0] + img_dxy[:, 0], img_cat.src_pos[:, 1] + img_dxy[:, 1])
     weights = drz_cat.src_weight if use_weights else None                  # align.py:703-716
     fit = _fit_from_shifts(img_dxy, status, xyim, xyref, weights, wcslin, fitgeom, nclip, sigma)
-    interlaced_cc = PackedImages(icc, offs_host, 2 * shapes, scale=4)
+    interlaced_cc = PackedImages(icc, offs_host, 2 * shapes, scale=4, dtype=img_cat.dtype)       # cc.py:121
     nonshifted_blts = PackedImages(im4, offs_host, shapes, scale=4, part=0)
     return fit, interlaced_cc, nonshifted_blts
 

@@ -186,13 +186,20 @@ def blot_affine4_batch(src, affine, shape, gain=None):
     return im4 if like_torch else im4.cpu().numpy()
 
 
-def blot4_packed(src, src_offsets, src_shapes, maps, dst_offsets, dst_shapes, dst_total, degree=0, gain=None):
+def blot4_packed(src, src_offsets, src_shapes, maps, dst_offsets, dst_shapes, dst_total, degree=0, gain=None,
+                 out_dtype=torch.float32):
     """The four dithered blots of every source of a packed catalog (``spx_blot4_var_f32``): ``src`` holds the
-    drizzled cutouts back to back (``cutout.pack_cutouts_var`` layout: ``src_offsets`` int64 [N],
+    float32 drizzled cutouts back to back (``cutout.pack_cutouts_var`` layout: ``src_offsets`` int64 [N],
     ``src_shapes`` int32 [N, 2] = (h, w)), the blots are made for image cutouts laid out by ``dst_offsets`` /
     ``dst_shapes`` (``dst_total`` pixels in all).  ``maps``: ``[N, 6]`` affines (``degree`` 0) or ``[N, 2, 21]``
-    polynomial coefficients (``degree`` 1..5).  Returns the flat float32 device buffer
-    ``[item][4][pixels]`` (item k at ``4 * dst_offsets[k]``)."""
+    polynomial coefficients (``degree`` 1..5).  Returns the flat device buffer ``[item][4][pixels]`` (item k at
+    ``4 * dst_offsets[k]``) of ``out_dtype``: float32, or float64 for float64 image cutouts
+    (``spx_blot4_var_to_f64``: blot.py:155 writes tblot's float32 result into a copy of the image cutout, so
+    the values are the float32 ones, widened)."""
+    if out_dtype not in (torch.float32, torch.float64):
+        raise ValueError("out_dtype must be torch.float32 or torch.float64.")
+    if src.dtype != torch.float32:
+        raise ValueError("src must be float32 (tblot resamples in float32, blot.py:134).")
     n = int(src_offsets.shape[0])
     degree = int(degree)
     m = np.asarray(maps, dtype=np.float64) if not isinstance(maps, torch.Tensor) else maps
@@ -206,10 +213,11 @@ def blot4_packed(src, src_offsets, src_shapes, maps, dst_offsets, dst_shapes, ds
                              else gain, torch.float32)
         if g.dim() != 1 or g.shape[0] != n:
             raise ValueError("gain must have shape [N].")
-    im4 = torch.empty((max(4 * int(dst_total), 1),), dtype=torch.float32, device=src.device)
+    im4 = torch.empty((max(4 * int(dst_total), 1),), dtype=out_dtype, device=src.device)
     lib = _ffi.load()
+    fn = lib.spx_blot4_var_to_f64 if out_dtype == torch.float64 else lib.spx_blot4_var_f32
     with torch.cuda.device(src.device):
-        _ffi.check(lib.spx_blot4_var_f32(device.ptr(src), device.ptr(src_offsets), device.ptr(src_shapes), n,
-                                         device.ptr(m), degree, device.ptr(g), device.ptr(dst_offsets),
-                                         device.ptr(dst_shapes), device.ptr(im4), device.stream_ptr()))
+        _ffi.check(fn(device.ptr(src), device.ptr(src_offsets), device.ptr(src_shapes), n, device.ptr(m), degree,
+                      device.ptr(g), device.ptr(dst_offsets), device.ptr(dst_shapes), device.ptr(im4),
+                      device.stream_ptr()))
     return im4

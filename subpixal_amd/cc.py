@@ -212,10 +212,14 @@ def find_displacement_packed(ref, im4, offsets, shapes, shapes_host, cc_type='NC
     (``spx_find_displacement5_catalog_f32``): ``ref`` float32 [total] holds the reference cutouts back to
     back (item k = ``shapes[k] = (h, w)`` pixels at ``offsets[k]``), ``im4`` float32 [4 total] their four
     blots at ``4 offsets[k]``; ``offsets`` / ``shapes`` are CUDA tensors, ``shapes_host`` the same shapes as a
-    numpy array (it only steers which kernel families are launched: no device round trip).
+    numpy array (it only steers which kernel families are launched: no device round trip).  A float64 ``ref``
+    takes float64 ``im4`` (``spx_find_displacement5_catalog_f64``: masks, statistics and normalisation in
+    float64, cc.py:131-156, before the float32 transforms).
 
     Returns CUDA tensors ``(dxdy [N, 2] float64, status [N] int32, icc float32 [4 total])``; items no kernel
     family takes (a side below 3 or above 128 px) keep ``(nan, nan)`` / status -1."""
+    if ref.dtype not in (torch.float32, torch.float64) or im4.dtype != ref.dtype:
+        raise ValueError("ref and im4 must both be float32 or both float64.")
     n = int(offsets.shape[0])
     dev = ref.device
     out = torch.full((n, 2), float('nan'), dtype=torch.float64, device=dev)
@@ -231,7 +235,9 @@ def find_displacement_packed(ref, im4, offsets, shapes, shapes_host, cc_type='NC
     lib = _ffi.load()
     with torch.cuda.device(dev):
         ws, ws_bytes = _workspace(lib.spx_workspace_bytes_xcorr(n, 128, 128) if mask & 8 else 0, dev)
-        _ffi.check(lib.spx_find_displacement5_catalog_f32(
+        fn = lib.spx_find_displacement5_catalog_f64 if ref.dtype == torch.float64 else \
+            lib.spx_find_displacement5_catalog_f32
+        _ffi.check(fn(
             device.ptr(ref), device.ptr(im4), device.ptr(offsets), device.ptr(shapes), n, mask,
             _cc_code(cc_type), device.ptr(out), device.ptr(status), device.ptr(icc), device.ptr(ws), ws_bytes,
             device.stream_ptr()))

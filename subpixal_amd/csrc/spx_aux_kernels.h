@@ -1,6 +1,6 @@
 // spx_aux_kernels.h -- kernels either side of the cross-correlation hot path:
 //   find_peak_kernel      centroid.find_peak in full generality (centroid.py:18-236)
-//   gather_cutouts_kernel frame -> fixed tiles (cutout.py:737-755, align.py:661)
+//   gather_cutouts_kernel frame -> fixed tiles (cutout.py:737-755, align.py:661), float32 or float64
 //   gen_pairs_kernel      synthetic Gaussian-spot pairs for bench / tests
 //   blot_affine4_kernel   the four half-pixel dithered blots of align.py:664-676 (poly5), affine map
 //   blot_poly4_kernel     the same for a polynomial (distorted) coordinate map, degree <= 5
@@ -65,11 +65,13 @@ void gen_pairs_kernel(uint64_t seed, int64_t first_index, int64_t nbatch, int n,
 // ---------------------------------------------------------------------------
 // seg/ids (optional): the segmentation image and the label of each box's source; pixels of
 // other labels are written as `fill` too (cutout.py:190: mask |= ~(seg == sid), then
-// align.py:661 zeroes the masked pixels).
+// align.py:661 zeroes the masked pixels).  T: the frame's pixel type (float32, or float64 for the catalog
+// path on float64 frames: cutout.py:698-701 keeps the data's dtype).
+template <typename T>
 SPX_TKERNEL(256)
-void gather_cutouts_kernel(const float* __restrict__ frame, const uint8_t* __restrict__ fmask,
+void gather_cutouts_kernel(const T* __restrict__ frame, const uint8_t* __restrict__ fmask,
                            int fny, int fnx, const int32_t* __restrict__ boxes, int64_t nbatch,
-                           int tny, int tnx, float fill, float* __restrict__ tiles,
+                           int tny, int tnx, T fill, T* __restrict__ tiles,
                            const int32_t* __restrict__ seg, const int32_t* __restrict__ ids) {
     const int64_t total = nbatch * tny * tnx;
     const int64_t step = rt::grid_size() * 256;
@@ -79,13 +81,13 @@ void gather_cutouts_kernel(const float* __restrict__ frame, const uint8_t* __res
         const int64_t b = i / ((int64_t)tnx * tny);
         const int x0 = boxes[4 * b], y0 = boxes[4 * b + 1];
         const int w = boxes[4 * b + 2], h = boxes[4 * b + 3];
-        float v = 0.0f;
+        T v = T(0);
         if (tx < w && ty < h) {
             const int fx = x0 + tx, fy = y0 + ty;
             v = fill;
             if (fx >= 0 && fx < fnx && fy >= 0 && fy < fny) {
-                const float f = frame[(int64_t)fy * fnx + fx];
-                const bool bad = (fmask && fmask[(int64_t)fy * fnx + fx]) || !(f - f == 0.0f) ||
+                const T f = frame[(int64_t)fy * fnx + fx];
+                const bool bad = (fmask && fmask[(int64_t)fy * fnx + fx]) || !(f - f == T(0)) ||
                                  (seg && seg[(int64_t)fy * fnx + fx] != ids[b]);
                 if (!bad) v = f;
             }
@@ -235,23 +237,24 @@ void blot_poly4_kernel(const float* __restrict__ src, int64_t nbatch, int sny, i
 // element off[p] of the output, row-major (h x w), its four blots at 4 off[p].  One workgroup per item
 // (grid-stride), so a 5000-source catalog is one launch and no host loop touches a pixel.
 // ---------------------------------------------------------------------------
+template <typename T>
 SPX_TKERNEL(256)
-void gather_cutouts_var_kernel(const float* __restrict__ frame, const uint8_t* __restrict__ fmask,
+void gather_cutouts_var_kernel(const T* __restrict__ frame, const uint8_t* __restrict__ fmask,
                                int fny, int fnx, const int32_t* __restrict__ boxes, int64_t nbatch,
-                               const int64_t* __restrict__ off, float fill, float* __restrict__ out,
+                               const int64_t* __restrict__ off, T fill, T* __restrict__ out,
                                const int32_t* __restrict__ seg, const int32_t* __restrict__ ids) {
     for (int64_t b = rt::block_id(); b < nbatch; b += rt::grid_size()) {
         const int x0 = boxes[4 * b], y0 = boxes[4 * b + 1];
         const int w = boxes[4 * b + 2], h = boxes[4 * b + 3];
-        float* dst = out + off[b];
+        T* dst = out + off[b];
         const int npx = w * h;
         for (int i = rt::thread_id(); i < npx; i += 256) {
             const int ty = i / w, tx = i - ty * w;
             const int fx = x0 + tx, fy = y0 + ty;
-            float v = fill;
+            T v = fill;
             if (fx >= 0 && fx < fnx && fy >= 0 && fy < fny) {
-                const float f = frame[(int64_t)fy * fnx + fx];
-                const bool bad = (fmask && fmask[(int64_t)fy * fnx + fx]) || !(f - f == 0.0f) ||
+                const T f = frame[(int64_t)fy * fnx + fx];
+                const bool bad = (fmask && fmask[(int64_t)fy * fnx + fx]) || !(f - f == T(0)) ||
                                  (seg && seg[(int64_t)fy * fnx + fx] != ids[b]);
                 if (!bad) v = f;
             }
@@ -262,21 +265,25 @@ void gather_cutouts_var_kernel(const float* __restrict__ frame, const uint8_t* _
 
 // the four dithered blots of every source from its own (variable-shape) drizzled cutout: `map` holds 6
 // doubles per source (degree 0: affine, as blot_affine4_kernel) or 2 x 21 (degree 1..5: polynomial, as
-// blot_poly4_kernel); the same arithmetic per output pixel as those kernels
+// blot_poly4_kernel); the same arithmetic per output pixel as those kernels.  TOut: the type the blots are
+// stored in -- the image cutouts' (blot.py:155 writes tblot's float32 result into a copy of the image
+// cutout); the samples, the resampling and `gain` stay float32 (blot.py:134), so a double output holds the
+// float32 result widened, exactly.
+template <typename TOut>
 SPX_TKERNEL(256)
 void blot4_var_kernel(const float* __restrict__ src, const int64_t* __restrict__ src_off,
                       const int32_t* __restrict__ src_shp, int64_t nbatch, const double* __restrict__ map,
                       int degree, const float* __restrict__ gain, const int64_t* __restrict__ dst_off,
-                      const int32_t* __restrict__ dst_shp, float* __restrict__ im4) {
+                      const int32_t* __restrict__ dst_shp, TOut* __restrict__ im4) {
     for (int64_t b = rt::block_id(); b < nbatch; b += rt::grid_size()) {
         const int sny = src_shp[2 * b], snx = src_shp[2 * b + 1];
         const int ny = dst_shp[2 * b], nx = dst_shp[2 * b + 1];
         const float* tile = src + src_off[b];
-        float* dst = im4 + 4 * dst_off[b];
+        TOut* dst = im4 + 4 * dst_off[b];
         const int npx = ny * nx;
         const float g = gain ? gain[b] : 1.0f;
         if (sny < 6 || snx < 6) {            // (the fixed-shape entry refuses such sources; here: no signal)
-            for (int i = rt::thread_id(); i < 4 * npx; i += 256) dst[i] = 0.0f;
+            for (int i = rt::thread_id(); i < 4 * npx; i += 256) dst[i] = TOut(0);
             continue;
         }
         const double xc = 0.5 * (double)(nx - 1), yc = 0.5 * (double)(ny - 1);
@@ -296,7 +303,7 @@ void blot4_var_kernel(const float* __restrict__ src, const int64_t* __restrict__
             }
             float v = blot_resample(tile, sny, snx, xs, ys);
             if (gain) v *= g;
-            dst[r] = v;
+            dst[r] = (TOut)v;
         }
     }
 }

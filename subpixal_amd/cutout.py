@@ -292,9 +292,19 @@ def primary_cutout_boxes(segmentation_image, ids=None, pad=1):
     return present.astype(np.int32), boxes
 
 
-def pack_cutouts(frame, boxes, tile, mask=None, fill=0.0, segmentation_image=None, ids=None):
+def _pixel_dtype(dtype):
+    """(torch dtype, float64?) of the pixel type a gather writes: float32 or float64, nothing else."""
+    dt = np.dtype(dtype)
+    if dt == np.float32:
+        return torch.float32, False
+    if dt == np.float64:
+        return torch.float64, True
+    raise ValueError("dtype must be float32 or float64, not %s." % dt)
+
+
+def pack_cutouts(frame, boxes, tile, mask=None, fill=0.0, segmentation_image=None, ids=None, dtype=np.float32):
     """Gather ``len(boxes)`` windows of ``frame [fny, fnx]`` into ``tiles [N, tny, tnx]``
-    float32 on the device.
+    of ``dtype`` (float32 or float64; the frame is converted to it) on the device.
 
     boxes : int ``[N, 4]`` rows ``(x0, y0, width, height)``; windows may overhang the
         frame.  mask : bad-pixel booleans ``[fny, fnx]`` (True = bad) or None.
@@ -304,7 +314,8 @@ def pack_cutouts(frame, boxes, tile, mask=None, fill=0.0, segmentation_image=Non
     the frame, the pixel is masked or it is not finite; the padding outside the window
     is 0 (which leaves the linear cross-correlation unchanged).
     """
-    f = device.to_device(frame, torch.float32)
+    tdt, f64 = _pixel_dtype(dtype)
+    f = device.to_device(frame, tdt)
     b = device.to_device(np.asarray(boxes, dtype=np.int32) if not isinstance(boxes, torch.Tensor)
                          else boxes, torch.int32)
     if f.dim() != 2 or b.dim() != 2 or b.shape[1] != 4:
@@ -322,13 +333,12 @@ def pack_cutouts(frame, boxes, tile, mask=None, fill=0.0, segmentation_image=Non
                                                    if not isinstance(ids, torch.Tensor) else ids, torch.int32)
     if sg is not None and (tuple(sg.shape) != tuple(f.shape) or si.shape[0] != b.shape[0]):
         raise ValueError("segmentation image must match the frame and ids the boxes.")
-    tiles = torch.empty((b.shape[0], tny, tnx), dtype=torch.float32, device=f.device)
+    tiles = torch.empty((b.shape[0], tny, tnx), dtype=tdt, device=f.device)
     lib = _ffi.load()
+    fn = lib.spx_gather_cutouts_f64 if f64 else lib.spx_gather_cutouts_f32
     with torch.cuda.device(f.device):
-        _ffi.check(lib.spx_gather_cutouts_f32(device.ptr(f), device.ptr(m), f.shape[0], f.shape[1],
-                                              device.ptr(b), b.shape[0], tny, tnx, float(fill),
-                                              device.ptr(tiles), device.ptr(sg), device.ptr(si),
-                                              device.stream_ptr()))
+        _ffi.check(fn(device.ptr(f), device.ptr(m), f.shape[0], f.shape[1], device.ptr(b), b.shape[0], tny, tnx,
+                      float(fill), device.ptr(tiles), device.ptr(sg), device.ptr(si), device.stream_ptr()))
     return tiles
 
 
@@ -341,14 +351,16 @@ def _item_tables(shapes):
     return offs, int(sizes.sum())
 
 
-def pack_cutouts_var(frame, boxes, mask=None, fill=0.0, segmentation_image=None, ids=None, _tables=None):
-    """Gather windows of DIFFERENT shapes of ``frame`` into one packed float32 device buffer
-    (``spx_gather_cutouts_var_f32``): item ``k`` = ``boxes[k] = (x0, y0, width, height)`` occupies
-    ``packed[offsets[k] : offsets[k] + height * width]``, row-major.  ``fill``, ``mask``,
-    ``segmentation_image`` / ``ids`` as :func:`pack_cutouts`.
+def pack_cutouts_var(frame, boxes, mask=None, fill=0.0, segmentation_image=None, ids=None, _tables=None,
+                     dtype=np.float32):
+    """Gather windows of DIFFERENT shapes of ``frame`` into one packed device buffer of ``dtype`` (float32:
+    ``spx_gather_cutouts_var_f32``, float64: ``spx_gather_cutouts_var_f64``; the frame is converted to it):
+    item ``k`` = ``boxes[k] = (x0, y0, width, height)`` occupies ``packed[offsets[k] : offsets[k] + height *
+    width]``, row-major.  ``fill``, ``mask``, ``segmentation_image`` / ``ids`` as :func:`pack_cutouts`.
 
-    Returns ``(packed, offsets, shapes)``: CUDA tensors (float32 [total], int64 [N], int32 [N, 2] = (h, w))."""
-    f = device.to_device(frame, torch.float32)
+    Returns ``(packed, offsets, shapes)``: CUDA tensors (``dtype`` [total], int64 [N], int32 [N, 2] = (h, w))."""
+    tdt, f64 = _pixel_dtype(dtype)
+    f = device.to_device(frame, tdt)
     boxes = np.ascontiguousarray(boxes, dtype=np.int32)
     if f.dim() != 2 or boxes.ndim != 2 or boxes.shape[1] != 4:
         raise ValueError("frame must be 2-D and boxes [N, 4].")
@@ -368,24 +380,27 @@ def pack_cutouts_var(frame, boxes, mask=None, fill=0.0, segmentation_image=None,
         _tables = (torch.from_numpy(boxes).to(f.device), torch.from_numpy(offs).to(f.device),
                    torch.from_numpy(shapes).to(f.device), total)
     b_d, o_d, s_d, total = _tables
-    packed = torch.empty((max(total, 1),), dtype=torch.float32, device=f.device)
+    packed = torch.empty((max(total, 1),), dtype=tdt, device=f.device)
     lib = _ffi.load()
+    fn = lib.spx_gather_cutouts_var_f64 if f64 else lib.spx_gather_cutouts_var_f32
     with torch.cuda.device(f.device):
-        _ffi.check(lib.spx_gather_cutouts_var_f32(device.ptr(f), device.ptr(m), f.shape[0], f.shape[1],
-                                                  device.ptr(b_d), boxes.shape[0], device.ptr(o_d), float(fill),
-                                                  device.ptr(packed), device.ptr(sg), device.ptr(si),
-                                                  device.stream_ptr()))
+        _ffi.check(fn(device.ptr(f), device.ptr(m), f.shape[0], f.shape[1], device.ptr(b_d), boxes.shape[0],
+                      device.ptr(o_d), float(fill), device.ptr(packed), device.ptr(sg), device.ptr(si),
+                      device.stream_ptr()))
     return packed, o_d, s_d
 
 
 class PackedImages(object):
-    """Read-only sequence of 2-D float32 images stored back to back in one device buffer (what the
+    """Read-only sequence of 2-D images stored back to back in one device buffer (what the
     catalog path of ``find_linear_fit`` returns for the interlaced cross-correlation images and the
-    non-shifted blots).  ``images[k]`` is a numpy array; the buffer is copied to the host once, on first
-    access -- a caller that never looks at them (the fit itself does not) pays nothing."""
+    non-shifted blots).  ``images[k]`` is a numpy array of ``dtype`` (default: the buffer's); the buffer is
+    copied to the host -- and converted, once, when ``dtype`` differs from the device buffer's, as for the
+    float32 interlaced images of a float64 catalog -- on first access: a caller that never looks at them (the
+    fit itself does not) pays nothing."""
 
-    def __init__(self, buf, offsets, shapes, scale=1, stride=1, part=0):
+    def __init__(self, buf, offsets, shapes, scale=1, stride=1, part=0, dtype=None):
         self._buf, self._host = buf, None
+        self._dtype = None if dtype is None else np.dtype(dtype)
         self._off = np.asarray(offsets, dtype=np.int64) * scale
         self._shp = np.asarray(shapes, dtype=np.int64)
         self._stride, self._part = stride, part         # blots: 4 images per item, `part` selects one
@@ -397,7 +412,8 @@ class PackedImages(object):
         if isinstance(k, slice):
             return [self[i] for i in range(*k.indices(len(self)))]
         if self._host is None:
-            self._host = self._buf.cpu().numpy()
+            host = self._buf.cpu().numpy()
+            self._host = host if self._dtype is None else host.astype(self._dtype, copy=False)
         k = int(k) + (len(self) if k < 0 else 0)
         h, w = self._shp[k]
         o = self._off[k] + self._part * h * w
@@ -422,20 +438,30 @@ class CutoutCatalog(object):
     src_weight : ``[N]`` or None.   src_id : ``[N]`` labels in ``segmentation_image`` (default 1..N).
     mask : bad-pixel booleans of the frame (True = bad).  segmentation_image : label image; pixels of a box
     carrying another label count as masked (cutout.py:190).  fillval : value of pixels outside the frame.
+    dtype : float32 (default) or float64, the pixel type the frame is kept in on the device and everything
+    computed from it: the packed cutouts, the blots made for them and the cross-correlation's masks and
+    statistics (``find_linear_fit``).  The reference computes in the cutouts' dtype -- that of its image
+    (cutout.py:698-701) -- so ``dtype=frame.dtype`` gives its semantics; float32 is the fast default.  A float32
+    frame is widened for float64.  ``catalog[k].data`` has this dtype too.
     """
 
     def __init__(self, frame, boxes, src_pos=None, src_weight=None, src_id=None, mask=None,
-                 segmentation_image=None, wcs=None, fillval=np.nan, exptime=1, data_units='rate'):
+                 segmentation_image=None, wcs=None, fillval=np.nan, exptime=1, data_units='rate',
+                 dtype=np.float32):
         self.boxes = np.ascontiguousarray(boxes, dtype=np.int32)
         if self.boxes.ndim != 2 or self.boxes.shape[1] != 4:
             raise ValueError("boxes must have shape [N, 4].")
         if (self.boxes[:, 2:] < 1).any():
             raise ValueError("Ill-formed extraction box: width and height must be positive.")
         n = len(self.boxes)
-        self.frame = device.to_device(frame, torch.float32)
+        tdt, _ = _pixel_dtype(dtype)
+        self.dtype = np.dtype(dtype)
+        self.frame = device.to_device(frame, tdt)
         if self.frame.dim() != 2:
             raise ValueError("frame must be 2-D.")
-        self._frame_host = frame if isinstance(frame, np.ndarray) else None
+        # the host frame of catalog[k], in the catalog's dtype: converted on first use
+        self._frame_np = frame if isinstance(frame, np.ndarray) else None
+        self._frame_host = frame if self._frame_np is not None and frame.dtype == self.dtype else None
         self._tables = None
         self.mask = None if mask is None else device.to_device(mask, torch.uint8)
         self.segmentation_image = None if segmentation_image is None else \
@@ -463,7 +489,8 @@ class CutoutCatalog(object):
 
     def _host_frame(self):
         if self._frame_host is None:
-            self._frame_host = self.frame.cpu().numpy()
+            self._frame_host = np.asarray(self._frame_np, dtype=self.dtype) if self._frame_np is not None \
+                else self.frame.cpu().numpy()
         return self._frame_host
 
     def __getitem__(self, k):
@@ -487,7 +514,8 @@ class CutoutCatalog(object):
         return (self[k] for k in range(len(self)))
 
     def packed(self, zero_masked=False):
-        """``(packed, offsets, shapes)`` device tensors of all cutouts (:func:`pack_cutouts_var`).
+        """``(packed, offsets, shapes)`` device tensors of all cutouts (:func:`pack_cutouts_var`), ``packed`` of
+        the catalog's dtype.
         zero_masked False: the cutouts' ``data`` -- frame pixels, ``fillval`` outside the frame;
         True: masked pixels (mask, other segments, non-finite, outside) zeroed, i.e. after align.py:661."""
         if self._tables is None:           # the box / offset / shape tables go to the device once
@@ -499,5 +527,6 @@ class CutoutCatalog(object):
             self._ids_dev = torch.from_numpy(self.src_id).to(dev)
         if zero_masked:
             return pack_cutouts_var(self.frame, self.boxes, self.mask, 0.0, self.segmentation_image,
-                                    None if self.segmentation_image is None else self._ids_dev, self._tables)
-        return pack_cutouts_var(self.frame, self.boxes, None, self.fillval, _tables=self._tables)
+                                    None if self.segmentation_image is None else self._ids_dev, self._tables,
+                                    dtype=self.dtype)
+        return pack_cutouts_var(self.frame, self.boxes, None, self.fillval, _tables=self._tables, dtype=self.dtype)

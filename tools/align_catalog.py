@@ -5,7 +5,10 @@ reference's 5-image `cc.find_displacement` (align.py:656-699), for a synthetic 4
 5000-source catalog -- device-resident: the frames live on the GPU, `cutout.CutoutCatalog` describes the
 cutouts by a box table, and the whole per-source loop is four kernel launches.
 
-    python tools/align_catalog.py [--size 4096] [--sources 5000]
+    python tools/align_catalog.py [--size 4096] [--sources 5000] [--dtype float32|float64]
+
+--dtype float64 renders both frames in float64 and runs both catalogs in float64 (the reference's semantics for
+float64 frames: it computes in the cutouts' dtype).
 """
 import argparse
 import os
@@ -20,8 +23,8 @@ sys.path.insert(0, os.path.join(ROOT, 'tools'))
 import align_synthetic                                      # noqa: E402  (scene + renderer)
 
 
-def build(size=4096, nsrc=5000, seed=5, margin=6, pad=3):
-    """Frames, segmentation, catalogs and maps.
+def build(size=4096, nsrc=5000, seed=5, margin=6, pad=3, dtype='float32'):
+    """Frames, segmentation, catalogs and maps (frames and catalogs in `dtype`).
 
     Sources sit on a jittered grid (no two closer than ~35 px), 98 % compact (sigma 4 px, segment = ellipse
     with semi-axes of 11..17 px) and 2 % extended (sigma 9..13 px, semi-axes 30..45 px, which swallow
@@ -52,8 +55,9 @@ def build(size=4096, nsrc=5000, seed=5, margin=6, pad=3):
     f[0, 1] += 1e-5
     t = np.array([0.731, -1.284])
     xy2 = (xy - c) @ f.T + c + t
-    drz_frame = np.zeros((size, size), np.float32)
-    img_frame = np.zeros((size, size), np.float32)
+    dtype = np.dtype(dtype)
+    drz_frame = np.zeros((size, size), dtype)
+    img_frame = np.zeros((size, size), dtype)
     seg = np.zeros((size, size), np.int32)
     for k in np.argsort(-radius, kind='stable'):              # extended sources first: compact ones on top
         for frame, (x, y) in ((drz_frame, xy[k]), (img_frame, xy2[k])):
@@ -62,7 +66,7 @@ def build(size=4096, nsrc=5000, seed=5, margin=6, pad=3):
             ix, iy = int(round(x)), int(round(y))
             gx = np.exp(-((gg + ix - x) ** 2) / (2 * sigma[k] ** 2))
             gy = np.exp(-((gg + iy - y) ** 2) / (2 * sigma[k] ** 2))
-            frame[iy - half:iy + half + 1, ix - half:ix + half + 1] += (amp[k] * np.outer(gy, gx)).astype(np.float32)
+            frame[iy - half:iy + half + 1, ix - half:ix + half + 1] += (amp[k] * np.outer(gy, gx)).astype(dtype)
         ax, ay = int(rx[k]), int(ry[k])
         gx, gy = np.arange(-ax, ax + 1), np.arange(-ay, ay + 1)
         ix, iy = int(round(xy[k, 0])), int(round(xy[k, 1]))
@@ -76,19 +80,20 @@ def build(size=4096, nsrc=5000, seed=5, margin=6, pad=3):
     iboxes[:, :2] += shift
     dboxes = boxes + np.array([-margin, -margin, 2 * margin, 2 * margin], np.int32)
     weights = rng.uniform(0.5, 2.0, len(k))
-    img_cat = cutout.CutoutCatalog(torch.from_numpy(img_frame).cuda(), iboxes, src_pos=xy2[k], src_id=ids)
+    img_cat = cutout.CutoutCatalog(torch.from_numpy(img_frame).cuda(), iboxes, src_pos=xy2[k], src_id=ids,
+                                   dtype=dtype)
     drz_cat = cutout.CutoutCatalog(torch.from_numpy(drz_frame).cuda(), dboxes, src_pos=xy[k], src_weight=weights,
-                                   src_id=ids, segmentation_image=seg_d)
+                                   src_id=ids, segmentation_image=seg_d, dtype=dtype)
     img_cat._frame_host, drz_cat._frame_host = img_frame, drz_frame      # (saves the D2H copy when cutouts are built)
     affine = blot.shift_affine(len(k), x0=(shift[:, 0] + margin).astype(np.float64),
                                y0=(shift[:, 1] + margin).astype(np.float64))
     return dict(img_cat=img_cat, drz_cat=drz_cat, affine=affine, xy=xy[k], xy2=xy2[k], f=f, t=t, c=c, compact=~big[k])
 
 
-def run(size=4096, nsrc=5000, reps=5, quiet=False, nclip=12, cc_type='NCC'):
+def run(size=4096, nsrc=5000, reps=5, quiet=False, nclip=12, cc_type='NCC', dtype='float32'):
     import torch
     from subpixal_amd.align import find_linear_fit, iter_linear_fit
-    s = build(size, nsrc)
+    s = build(size, nsrc, dtype=dtype)
     times = []
     for _ in range(reps + 1):
         torch.cuda.synchronize()
@@ -106,8 +111,8 @@ def run(size=4096, nsrc=5000, reps=5, quiet=False, nclip=12, cc_type='NCC'):
     nsrc = len(d)
     if not quiet:
         shp = s['img_cat'].shapes
-        print('sources %d, frame %dx%d, %d distinct cutout shapes (%d..%d px per side), %s'
-              % (nsrc, size, size, len({tuple(x) for x in shp}), shp.min(), shp.max(), cc_type))
+        print('sources %d, frame %dx%d, %d distinct cutout shapes (%d..%d px per side), %s, %s'
+              % (nsrc, size, size, len({tuple(x) for x in shp}), shp.min(), shp.max(), cc_type, np.dtype(dtype)))
         print('find_linear_fit(CutoutCatalog, CutoutCatalog): first call %.2f ms, warm %.2f ms (median of %d)'
               % (1e3 * times[0], 1e3 * out['warm_s'], reps))
         print('|shift - truth|: median %.2e, 90%% %.2e px (compact sources: 99%% %.2e); kept %d of %d'
@@ -121,5 +126,6 @@ if __name__ == '__main__':
     ap = argparse.ArgumentParser()
     ap.add_argument('--size', type=int, default=4096)
     ap.add_argument('--sources', type=int, default=5000)
+    ap.add_argument('--dtype', choices=('float32', 'float64'), default='float32')
     a = ap.parse_args()
-    run(a.size, a.sources)
+    run(a.size, a.sources, dtype=a.dtype)

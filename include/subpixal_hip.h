@@ -24,6 +24,9 @@
  *                                   + masked-pixel zeroing        subpixal/align.py:661.
  *   spx_label_bboxes_i32        <-  per-source bounding boxes from the segmentation image
  *                                   subpixal/cutout.py:151-160 (one pass for all sources).
+ *   spx_detect_label_f32 / _f64, spx_measure_labels_f32 / _f64
+ *                               <-  the source finder the reference shells out to (catalogs.py:
+ *                                   SExImageCatalog): segmentation image and isophotal measurements.
  *   spx_blot_affine4_f32        <-  the four blot_cutout(dzct, imct) calls per source of
  *                                   subpixal/align.py:664-676 (blot.py:79-155, drizzlepac
  *                                   tblot, interp='poly5') for coordinate maps that are
@@ -294,6 +297,61 @@ int spx_gather_cutouts_f64(const double* frame, const uint8_t* fmask, int fny, i
  */
 int spx_label_bboxes_i32(const int32_t* seg, int fny, int fnx, int32_t max_label,
                          int32_t* boxes, int32_t* counts, void* stream);
+
+/*
+ * Source finding (what the reference leaves to SExtractor, catalogs.py: SExImageCatalog): detection
+ * threshold -> connected-component labelling -> minimum area -> labels 1..L in raster order of each
+ * component's first pixel, i.e. the numbering of scipy.ndimage.label followed by dropping the small
+ * components and closing the gaps.
+ *   detected(y,x) = finite(v) && !bad_mask(y,x) && f(y,x) > thr(y,x)          (strict >)
+ *   frame      : float32 / float64 [fny][fnx];  bad_mask : uint8 [fny][fnx] (non-zero = bad) or NULL
+ *   thr        : thr_map (FLOAT32 [fny][fnx], for both entries) when given, else thr_scalar
+ *   filter     : NULL (f = v; fky = fkx = 1), or [fky][fkx] weights in the frame's dtype, odd sides <= 7,
+ *                centred: f(y,x) = sum_j sum_i filter[j][i] v'(y + j - fky/2, x + i - fkx/2), where v' = 0
+ *                for pixels outside the frame, masked or not finite.  The weights are used as given (the
+ *                caller normalises them; nothing is renormalised where pixels drop out); the sum is one
+ *                fused multiply-add chain in the frame's dtype, row-major over the filter.
+ *   connectivity : 8 or 4;  min_area >= 1: components with fewer pixels are erased (label 0)
+ *   work       : spx_detect_workspace_bytes(fny, fnx) bytes of device memory (two int32 frames for the
+ *                roots and the per-root counts, the scan's partial sums, a status word); too small or
+ *                NULL: SPX_E_WORKSPACE, and nothing is written
+ *   out_labels : int32 [fny][fnx] (also holds the parent links while components are merged)
+ *   out_nlabels: int32 [1] on the DEVICE: L, or -1 if a merge chain failed its consistency check (no
+ *                schedule can produce that from valid inputs; out_labels is undefined then)
+ * SPX_E_ARG: null pointer, connectivity not 4 / 8, even filter side or side > 7, min_area < 1;
+ * SPX_E_SHAPE: fny or fnx < 1, or fny * fnx >= 2^31 - 1.  Results do not depend on scheduling.
+ */
+size_t spx_detect_workspace_bytes(int fny, int fnx);
+int spx_detect_label_f32(const float* frame, const uint8_t* bad_mask, float thr_scalar, const float* thr_map,
+                         const float* filter, int fky, int fkx, int fny, int fnx, int connectivity,
+                         int min_area, void* work, size_t work_bytes, int32_t* out_labels,
+                         int32_t* out_nlabels, void* stream);
+int spx_detect_label_f64(const double* frame, const uint8_t* bad_mask, double thr_scalar, const float* thr_map,
+                         const double* filter, int fky, int fkx, int fny, int fnx, int connectivity,
+                         int min_area, void* work, size_t work_bytes, int32_t* out_labels,
+                         int32_t* out_nlabels, void* stream);
+
+/*
+ * Isophotal measurements of labels 1..nlabels of a label image, on the UNFILTERED frame, with
+ * w = v - bkg (bkg_map in the frame's dtype when given, else bkg_scalar) over the label's pixels.
+ *   boxes         : int32 [nlabels + 1][4], the table spx_label_bboxes_i32 writes (row = label)
+ *   out_table_f64 : float64 [nlabels][SPX_MEASURE_COLUMNS], row l - 1 = (npix, flux, x, y, x2, y2, xy, a, b,
+ *                   theta, peak, xpeak, ypeak): flux = sum w; x, y = flux-weighted centre (0-based pixel
+ *                   centres); x2, y2, xy = central second moments; a, b, theta (degrees, in (-90, 90]) =
+ *                   the moments' ellipse as SExtractor's A_IMAGE, B_IMAGE, THETA_IMAGE define it (a^2, b^2 =
+ *                   (x2 + y2)/2 +- sqrt(((x2 - y2)/2)^2 + xy^2), tan 2 theta = 2 xy / (x2 - y2)); peak =
+ *                   max w at (xpeak, ypeak), the first maximum in raster order
+ *   out_flags_i32 : int32 [nlabels]: bit 0 the segment touches the frame border, bit 1 flux <= 0 (x, y,
+ *                   moments and ellipse are NaN), bit 2 a masked or non-finite pixel lies inside the box
+ * All sums are float64 in a fixed order: results are bit-identical from run to run.
+ */
+#define SPX_MEASURE_COLUMNS 13
+int spx_measure_labels_f32(const float* frame, const uint8_t* bad_mask, double bkg_scalar, const float* bkg_map,
+                           const int32_t* labels, int fny, int fnx, int nlabels, const int32_t* boxes,
+                           double* out_table_f64, int32_t* out_flags_i32, void* stream);
+int spx_measure_labels_f64(const double* frame, const uint8_t* bad_mask, double bkg_scalar, const double* bkg_map,
+                           const int32_t* labels, int fny, int fnx, int nlabels, const int32_t* boxes,
+                           double* out_table_f64, int32_t* out_flags_i32, void* stream);
 
 /*
  * Half-pixel dithered blots: for every source the four images image00, image10, image01,

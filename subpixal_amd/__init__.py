@@ -9,7 +9,8 @@ from . import _ffi                                           # noqa: F401
 from .cc import find_displacement, find_displacement_batch, find_displacement_var, xcorr_refine_batch
 from .centroid import find_peak, find_peak_batch
 from .utils import py2round
+from . import detect                                         # noqa: F401  (source finding)
 
 __version__ = '0.1.0'
 __all__ = ['find_displacement', 'find_displacement_batch', 'find_displacement_var', 'xcorr_refine_batch',
-           'find_peak', 'find_peak_batch', 'py2round']
+           'find_peak', 'find_peak_batch', 'py2round', 'detect']

@@ -11,6 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('SPX_HIP_LIB') or os.path.join(_HERE, 'csrc', 'libsubpixal_hip.so')
 
 ABI_VERSION = 4
+MEASURE_COLUMNS = 13                                     # SPX_MEASURE_COLUMNS
 REFINE_DEFAULT, REFINE_F64, REFINE_F32 = 0, 1, 2         # SPX_REFINE_* (include/subpixal_hip.h)
 MAX_SIDE = 682
 MAX_UPSAMPLE = 59
@@ -68,6 +69,16 @@ _SIGNATURES = {
     'spx_gather_cutouts_f64': (_c.c_int, [_vp, _vp, _c.c_int, _c.c_int, _vp, _c.c_int64,
                                           _c.c_int, _c.c_int, _c.c_double, _vp, _vp, _vp, _vp]),
     'spx_label_bboxes_i32': (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int32, _vp, _vp, _vp]),
+    # source finding: segmentation image (spx_detect_label_*) and isophotal measurements (spx_measure_labels_*)
+    'spx_detect_workspace_bytes': (_c.c_size_t, [_c.c_int, _c.c_int]),
+    'spx_detect_label_f32': (_c.c_int, [_vp, _vp, _c.c_float, _vp, _vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
+                                        _c.c_int, _c.c_int, _vp, _c.c_size_t, _vp, _vp, _vp]),
+    'spx_detect_label_f64': (_c.c_int, [_vp, _vp, _c.c_double, _vp, _vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
+                                        _c.c_int, _c.c_int, _vp, _c.c_size_t, _vp, _vp, _vp]),
+    'spx_measure_labels_f32': (_c.c_int, [_vp, _vp, _c.c_double, _vp, _vp, _c.c_int, _c.c_int, _c.c_int, _vp, _vp,
+                                          _vp, _vp]),
+    'spx_measure_labels_f64': (_c.c_int, [_vp, _vp, _c.c_double, _vp, _vp, _c.c_int, _c.c_int, _c.c_int, _vp, _vp,
+                                          _vp, _vp]),
     'spx_blot_affine4_f32': (_c.c_int, [_vp, _c.c_int64, _c.c_int, _c.c_int, _vp, _vp, _c.c_int,
                                         _c.c_int, _vp, _vp]),
     'spx_blot_poly4_f32': (_c.c_int, [_vp, _c.c_int64, _c.c_int, _c.c_int, _vp, _c.c_int, _vp, _c.c_int,

@@ -8,6 +8,7 @@
 #include "spx_kernels_big.h"
 #include "spx_kernels32.h"
 #include "spx_aux_kernels.h"
+#include "spx_detect_kernels.h"
 #include "spx_tables.h"
 #include "../../include/subpixal_hip.h"
 
@@ -1061,6 +1062,134 @@ int spx_gen_gaussian_pairs_f32(uint64_t seed, int64_t first_index, int64_t nbatc
                        sigma_hi, max_shift, ref, img, truth_dxdy);
     SPX_HIP(hipGetLastError());
     return 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------
+// source finding (spx_detect_kernels.h).  Workspace: R int32 [npix] | cnt int32 [npix] | chunk sums int32
+// [ceil(npix / 1024)] | status int32, each part on a 256-byte boundary.
+// ---------------------------------------------------------------------------------------------------------
+namespace {
+struct DetectLayout {
+    size_t r, cnt, sums, status, total;
+};
+DetectLayout detect_layout(int64_t npix) {
+    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+    DetectLayout d;
+    d.r = 0;
+    d.cnt = up((size_t)npix * 4);
+    d.sums = d.cnt + up((size_t)npix * 4);
+    d.status = d.sums + up((size_t)((npix + spx::kDetChunk - 1) / spx::kDetChunk) * 4);
+    d.total = d.status + 256;
+    return d;
+}
+unsigned capped_grid(int64_t blocks, int64_t cap = 65536) {
+    return (unsigned)(blocks < 1 ? 1 : (blocks < cap ? blocks : cap));
+}
+
+template <typename T>
+int detect_label(const T* frame, const uint8_t* bad, T thr_scalar, const float* thr_map, const T* filter, int fky,
+                 int fkx, int fny, int fnx, int conn, int min_area, void* work, size_t work_bytes,
+                 int32_t* out_labels, int32_t* out_nlabels, void* stream) {
+    if (!frame || !out_labels || !out_nlabels) return fail(SPX_E_ARG, "null pointer");
+    if (fny < 1 || fnx < 1 || (int64_t)fny * fnx >= 2147483647LL)
+        return fail(SPX_E_SHAPE, "the frame must hold 1 .. 2^31 - 2 pixels");
+    if (conn != 4 && conn != 8) return fail(SPX_E_ARG, "connectivity must be 4 or 8");
+    if (min_area < 1) return fail(SPX_E_ARG, "min_area must be at least 1");
+    if (!filter) fky = fkx = 1;
+    if (fky < 1 || fkx < 1 || !(fky & 1) || !(fkx & 1) || fky > spx::kDetMaxFilter || fkx > spx::kDetMaxFilter)
+        return fail(SPX_E_ARG, "filter sides must be odd and at most 7");
+    const int npix = fny * fnx;
+    const DetectLayout lay = detect_layout(npix);
+    if (!work || work_bytes < lay.total)
+        return fail(SPX_E_WORKSPACE, "workspace missing or smaller than spx_detect_workspace_bytes(fny, fnx)");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    char* w = static_cast<char*>(work);
+    int32_t* R = reinterpret_cast<int32_t*>(w + lay.r);
+    int32_t* cnt = reinterpret_cast<int32_t*>(w + lay.cnt);
+    int32_t* sums = reinterpret_cast<int32_t*>(w + lay.sums);
+    int32_t* status = reinterpret_cast<int32_t*>(w + lay.status);
+    SPX_HIP(hipMemsetAsync(status, 0, 4, s));
+    const int64_t ntiles = (int64_t)((fnx + spx::kDetTW - 1) / spx::kDetTW) * ((fny + spx::kDetTH - 1) / spx::kDetTH);
+    hipLaunchKernelGGL(spx::detect_tile_kernel<T>, dim3(capped_grid(ntiles, 1 << 20)), dim3(256),
+                       spx::det_tile_lds_bytes(sizeof(T), fky, fkx), s, frame, bad, thr_scalar, thr_map, filter,
+                       fky, fkx, fny, fnx, conn, out_labels, cnt, status);
+    SPX_HIP(hipGetLastError());
+    const int64_t nborder = (int64_t)((fny + spx::kDetTH - 1) / spx::kDetTH - 1) * fnx +
+                            2 * (int64_t)((fnx + spx::kDetTW - 1) / spx::kDetTW - 1) * fny;
+    if (nborder > 0) {
+        hipLaunchKernelGGL(spx::detect_border_kernel, dim3(capped_grid((nborder + 255) / 256)), dim3(256), 0, s,
+                           out_labels, fny, fnx, conn, status);
+        SPX_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(spx::detect_compress_kernel, dim3(capped_grid(((int64_t)npix + 1023) / 1024)), dim3(256), 0,
+                       s, out_labels, npix, R, cnt, status);
+    SPX_HIP(hipGetLastError());
+    const int64_t nchunks = ((int64_t)npix + spx::kDetChunk - 1) / spx::kDetChunk;
+    hipLaunchKernelGGL(spx::detect_flag_count_kernel, dim3(capped_grid(nchunks)), dim3(256), spx::kDetScanLdsBytes,
+                       s, R, cnt, npix, min_area, sums);
+    SPX_HIP(hipGetLastError());
+    hipLaunchKernelGGL(spx::detect_scan_blocks_kernel, dim3(1), dim3(256), spx::kDetScanLdsBytes, s, sums, nchunks,
+                       status, out_nlabels);
+    SPX_HIP(hipGetLastError());
+    hipLaunchKernelGGL(spx::detect_assign_kernel, dim3(capped_grid(nchunks)), dim3(256), spx::kDetScanLdsBytes, s,
+                       R, cnt, npix, min_area, sums);
+    SPX_HIP(hipGetLastError());
+    hipLaunchKernelGGL(spx::detect_relabel_kernel, dim3(capped_grid(((int64_t)npix + 255) / 256)), dim3(256), 0, s,
+                       R, cnt, npix, out_labels);
+    SPX_HIP(hipGetLastError());
+    return 0;
+}
+
+template <typename T>
+int measure_labels(const T* frame, const uint8_t* bad, double bkg_scalar, const T* bkg_map, const int32_t* labels,
+                   int fny, int fnx, int nlabels, const int32_t* boxes, double* table, int32_t* flags,
+                   void* stream) {
+    if (nlabels < 0) return fail(SPX_E_ARG, "negative label count");
+    if (fny < 1 || fnx < 1 || (int64_t)fny * fnx >= 2147483647LL)
+        return fail(SPX_E_SHAPE, "the frame must hold 1 .. 2^31 - 2 pixels");
+    if (nlabels == 0) return 0;
+    if (!frame || !labels || !boxes || !table || !flags) return fail(SPX_E_ARG, "null pointer");
+    hipLaunchKernelGGL(spx::measure_labels_kernel<T>, dim3(capped_grid(nlabels, 1 << 20)), dim3(256),
+                       spx::kMeasureLdsBytes, reinterpret_cast<hipStream_t>(stream), frame, bad, bkg_scalar, bkg_map,
+                       labels, fny, fnx, nlabels, boxes, table, flags);
+    SPX_HIP(hipGetLastError());
+    return 0;
+}
+}  // namespace
+
+extern "C" {
+
+size_t spx_detect_workspace_bytes(int fny, int fnx) {
+    if (fny < 1 || fnx < 1 || (int64_t)fny * fnx >= 2147483647LL) return 0;
+    return detect_layout((int64_t)fny * fnx).total;
+}
+int spx_detect_label_f32(const float* frame, const uint8_t* bad_mask, float thr_scalar, const float* thr_map,
+                         const float* filter, int fky, int fkx, int fny, int fnx, int connectivity,
+                         int min_area, void* work, size_t work_bytes, int32_t* out_labels,
+                         int32_t* out_nlabels, void* stream) {
+    return detect_label<float>(frame, bad_mask, thr_scalar, thr_map, filter, fky, fkx, fny, fnx, connectivity,
+                               min_area, work, work_bytes, out_labels, out_nlabels, stream);
+}
+int spx_detect_label_f64(const double* frame, const uint8_t* bad_mask, double thr_scalar, const float* thr_map,
+                         const double* filter, int fky, int fkx, int fny, int fnx, int connectivity,
+                         int min_area, void* work, size_t work_bytes, int32_t* out_labels,
+                         int32_t* out_nlabels, void* stream) {
+    return detect_label<double>(frame, bad_mask, thr_scalar, thr_map, filter, fky, fkx, fny, fnx, connectivity,
+                                min_area, work, work_bytes, out_labels, out_nlabels, stream);
+}
+int spx_measure_labels_f32(const float* frame, const uint8_t* bad_mask, double bkg_scalar, const float* bkg_map,
+                           const int32_t* labels, int fny, int fnx, int nlabels, const int32_t* boxes,
+                           double* out_table_f64, int32_t* out_flags_i32, void* stream) {
+    return measure_labels<float>(frame, bad_mask, bkg_scalar, bkg_map, labels, fny, fnx, nlabels, boxes,
+                                 out_table_f64, out_flags_i32, stream);
+}
+int spx_measure_labels_f64(const double* frame, const uint8_t* bad_mask, double bkg_scalar, const double* bkg_map,
+                           const int32_t* labels, int fny, int fnx, int nlabels, const int32_t* boxes,
+                           double* out_table_f64, int32_t* out_flags_i32, void* stream) {
+    return measure_labels<double>(frame, bad_mask, bkg_scalar, bkg_map, labels, fny, fnx, nlabels, boxes,
+                                  out_table_f64, out_flags_i32, stream);
 }
 
 }  // extern "C"

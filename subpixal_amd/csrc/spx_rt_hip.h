@@ -92,6 +92,12 @@ SPX_DEVICE void atomic_add_u64(unsigned long long* p, unsigned long long v) { at
 SPX_DEVICE void atomic_min_i32(int* p, int v) { atomicMin(p, v); }
 SPX_DEVICE void atomic_max_i32(int* p, int v) { atomicMax(p, v); }
 SPX_DEVICE void atomic_add_i32(int* p, int v) { atomicAdd(p, v); }
+// for the union-find of spx_detect_kernels.h (LDS or global): the min that returns the previous value, and a
+// load that other workgroups' atomics are visible to (device scope: served by L2, not by a CU's own cache)
+SPX_DEVICE int atomic_min_ret_i32(int* p, int v) { return atomicMin(p, v); }
+SPX_DEVICE int atomic_load_i32(const int* p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
 
 // ---------------------------------------------------------------------------
 // Packed complex arithmetic on (re, im) register pairs: one VOP3P instruction each,

@@ -1,0 +1,179 @@
+"""Source finding on the device: detection threshold -> connected-component labelling -> isophotal
+measurements -> the ``cutout.CutoutCatalog`` that ``align.find_linear_fit`` takes.
+
+The reference gets its segmentation image and source positions from SExtractor, an external program
+(``catalogs.py``: ``SExImageCatalog``); this module is the device-resident stand-in for that step.  Its
+definitions are its own (``include/subpixal_hip.h``, ``csrc/spx_detect_kernels.h``): parity with SExtractor is
+unpinned, and there is no deblending, background estimation or catalogue filter language here.
+"""
+import numpy as np
+import torch
+
+from . import _ffi, cutout, device
+
+COLUMNS = ('npix', 'flux', 'x', 'y', 'x2', 'y2', 'xy', 'a', 'b', 'theta', 'peak', 'xpeak', 'ypeak')
+FLAG_BORDER, FLAG_NOFLUX, FLAG_BADPIX = 1, 2, 4
+MAX_FILTER_SIDE = 7
+
+
+def _is_f64(frame):
+    if isinstance(frame, torch.Tensor):
+        return frame.dtype == torch.float64
+    return np.asarray(frame).dtype == np.float64
+
+
+def _frame_or_scalar(v, shape, tdt, name):
+    """(scalar, None) or (0.0, CUDA tensor of `tdt` and the frame's shape)"""
+    if isinstance(v, torch.Tensor) or np.ndim(v) > 0:
+        if tuple(np.shape(v)) != tuple(shape):
+            raise ValueError("%s must be a scalar or have the shape of the frame." % name)
+        return 0.0, device.to_device(v, tdt)
+    return float(v), None
+
+
+def _check_arguments(frame, mask, filter_kernel, min_area, connectivity):
+    """Everything that can be refused without touching the device."""
+    if frame.ndim != 2:
+        raise ValueError("frame must be 2-D.")
+    if frame.shape[0] < 1 or frame.shape[1] < 1 or frame.shape[0] * frame.shape[1] >= 2 ** 31 - 1:
+        raise ValueError("frame must hold between 1 and 2**31 - 2 pixels.")
+    if connectivity not in (4, 8):
+        raise ValueError("connectivity must be 4 or 8.")
+    if int(min_area) != min_area or min_area < 1:
+        raise ValueError("min_area must be an integer >= 1.")
+    if mask is not None and tuple(np.shape(mask)) != tuple(frame.shape):
+        raise ValueError("mask must have the shape of the frame.")
+    if filter_kernel is not None:
+        k = filter_kernel
+        if k.ndim != 2 or k.shape[0] % 2 == 0 or k.shape[1] % 2 == 0:
+            raise ValueError("filter_kernel must be 2-D with odd sides.")
+        if max(k.shape) > MAX_FILTER_SIDE:
+            raise ValueError("filter_kernel sides must be at most %d." % MAX_FILTER_SIDE)
+
+
+class Sources(object):
+    """What :func:`find_sources` found.  ``segmentation``: int32 CUDA tensor ``[ny, nx]`` with labels
+    ``1..len(self)`` in raster order of each segment's first pixel.  Per source (numpy, index = label - 1):
+    ``id``, ``x``, ``y`` (0-based pixel centres, the convention of ``CutoutCatalog.src_pos``), ``flux``,
+    ``npix``, central moments ``x2, y2, xy``, ellipse ``a, b, theta`` (degrees), ``peak`` at ``xpeak, ypeak``,
+    ``flags`` (``FLAG_BORDER | FLAG_NOFLUX | FLAG_BADPIX``) and ``bbox`` = (xmin, ymin, xmax, ymax) inclusive.
+    ``table_device`` / ``flags_device`` are the same numbers as CUDA tensors."""
+
+    def __init__(self, segmentation, table, flags, bbox):
+        self.segmentation = segmentation
+        self.table_device, self.flags_device = table, flags
+        t = table.cpu().numpy()
+        for i, c in enumerate(COLUMNS):
+            setattr(self, c, t[:, i].astype(np.int32) if c in ('npix', 'xpeak', 'ypeak') else t[:, i].copy())
+        self.flags = flags.cpu().numpy()
+        self.bbox = bbox.cpu().numpy()
+        self.id = np.arange(1, len(self.flags) + 1, dtype=np.int32)
+
+    def __len__(self):
+        return len(self.id)
+
+    def table(self):
+        """Columns under the names the reference's catalogs use (catalogs.py:75-93) where it has one."""
+        out = {'id': self.id, 'x': self.x, 'y': self.y, 'flux': self.flux, 'semi-major-a': self.a,
+               'semi-major-b': self.b}
+        for c in ('npix', 'x2', 'y2', 'xy', 'theta', 'peak', 'xpeak', 'ypeak', 'flags'):
+            out[c] = getattr(self, c)
+        return out
+
+    def cutout_catalog(self, frame, pad=1, dtype=np.float32, weight=None, mask=None):
+        """The primary cutouts of ``frame`` as a :class:`cutout.CutoutCatalog`, by the reference's rules
+        (``cutout.primary_cutout_boxes``: segments touching the border are skipped, box = bounding rectangle +
+        ``pad``), with ``src_pos = (x, y)``, ``src_id`` and this segmentation.  ``weight=None``: no source weights
+        (what the reference's ``compute_weights`` amounts to for equal weights); ``weight='flux'``: the fluxes.
+        Sources without a position (``FLAG_NOFLUX``) are left out."""
+        if weight not in (None, 'flux'):
+            raise ValueError("weight must be None or 'flux'.")
+        ids, boxes = cutout.primary_cutout_boxes(self.segmentation, pad=pad)
+        keep = (self.flags[ids - 1] & FLAG_NOFLUX) == 0
+        ids, boxes = ids[keep], boxes[keep]
+        k = ids - 1
+        return cutout.CutoutCatalog(frame, boxes, src_pos=np.stack([self.x[k], self.y[k]], axis=1),
+                                    src_weight=None if weight is None else self.flux[k], src_id=ids, mask=mask,
+                                    segmentation_image=self.segmentation, dtype=dtype)
+
+
+def label(frame, threshold, mask=None, filter_kernel=None, min_area=5, connectivity=8):
+    """Segmentation image only: ``(labels int32 CUDA [ny, nx], nlabels)`` (``spx_detect_label_f32/_f64``).
+    Arguments as :func:`find_sources`."""
+    fshape = frame if isinstance(frame, torch.Tensor) else np.asarray(frame)
+    kern = None if filter_kernel is None else np.asarray(filter_kernel)
+    _check_arguments(fshape, mask, kern, min_area, connectivity)
+    f64 = _is_f64(frame)
+    tdt = torch.float64 if f64 else torch.float32
+    f = device.to_device(frame, tdt)
+    thr, thr_map = _frame_or_scalar(threshold, f.shape, torch.float32, 'threshold')
+    m = None if mask is None else device.to_device(mask, torch.uint8)
+    k = None if kern is None else device.to_device(kern, tdt)
+    fky, fkx = (1, 1) if kern is None else kern.shape
+    ny, nx = f.shape
+    lib = _ffi.load()
+    nbytes = lib.spx_detect_workspace_bytes(ny, nx)
+    work = torch.empty((nbytes,), dtype=torch.uint8, device=f.device)
+    labels = torch.empty((ny, nx), dtype=torch.int32, device=f.device)
+    nlab = torch.empty((1,), dtype=torch.int32, device=f.device)
+    fn = lib.spx_detect_label_f64 if f64 else lib.spx_detect_label_f32
+    with torch.cuda.device(f.device):
+        _ffi.check(fn(device.ptr(f), device.ptr(m), thr, device.ptr(thr_map), device.ptr(k), int(fky), int(fkx),
+                      ny, nx, int(connectivity), int(min_area), device.ptr(work), nbytes, device.ptr(labels),
+                      device.ptr(nlab), device.stream_ptr()))
+    n = int(nlab.item())
+    if n < 0:
+        raise _ffi.SubpixalHipError("component merge failed its consistency check (spx_detect_label).")
+    return labels, n
+
+
+def measure(frame, labels, nlabels, background=0.0, mask=None):
+    """Isophotal measurements of labels ``1..nlabels`` (``spx_label_bboxes_i32`` + ``spx_measure_labels_f32/_f64``).
+    Returns CUDA tensors ``(table float64 [nlabels, 13] in COLUMNS order, flags int32 [nlabels], bbox int32
+    [nlabels, 4])``."""
+    f64 = _is_f64(frame)
+    tdt = torch.float64 if f64 else torch.float32
+    f = device.to_device(frame, tdt)
+    seg = device.to_device(labels, torch.int32)
+    if f.dim() != 2 or tuple(seg.shape) != tuple(f.shape):
+        raise ValueError("frame must be 2-D and labels must have its shape.")
+    if mask is not None and tuple(np.shape(mask)) != tuple(f.shape):
+        raise ValueError("mask must have the shape of the frame.")
+    bkg, bkg_map = _frame_or_scalar(background, f.shape, tdt, 'background')
+    m = None if mask is None else device.to_device(mask, torch.uint8)
+    boxes, _ = cutout.segment_bounding_boxes(seg, max_label=nlabels)
+    table = torch.empty((nlabels, len(COLUMNS)), dtype=torch.float64, device=f.device)
+    flags = torch.empty((nlabels,), dtype=torch.int32, device=f.device)
+    lib = _ffi.load()
+    fn = lib.spx_measure_labels_f64 if f64 else lib.spx_measure_labels_f32
+    with torch.cuda.device(f.device):
+        _ffi.check(fn(device.ptr(f), device.ptr(m), bkg, device.ptr(bkg_map), device.ptr(seg), f.shape[0],
+                      f.shape[1], int(nlabels), device.ptr(boxes), device.ptr(table), device.ptr(flags),
+                      device.stream_ptr()))
+    return table, flags, boxes[1:]
+
+
+def find_sources(frame, threshold, background=0.0, mask=None, filter_kernel=None, min_area=5, connectivity=8):
+    """Detect, label and measure the sources of ``frame`` on the device.
+
+    frame : 2-D numpy array or CUDA tensor; float64 frames are processed in float64, everything else in float32.
+    threshold : scalar, or a per-pixel frame (used as float32).  A pixel is detected when it is finite, not
+        masked and its (filtered) value is ``> threshold``.
+    background : scalar or per-pixel frame subtracted for the MEASUREMENTS (which use the unfiltered frame);
+        detection compares against ``threshold`` alone.
+    mask : booleans ``[ny, nx]``, True = bad, or None.
+    filter_kernel : 2-D weights with odd sides <= 7 the frame is correlated with before thresholding, used as
+        given (normalise them yourself); pixels outside the frame, masked or non-finite count as 0 and the
+        weights are not renormalised there.
+    min_area : components with fewer pixels are dropped.  connectivity : 8 or 4.
+
+    Returns a :class:`Sources`.  Labels are numbered in raster order of each component's first pixel, as
+    ``scipy.ndimage.label`` numbers them; all results are bit-identical from run to run."""
+    _check_arguments(frame if isinstance(frame, torch.Tensor) else np.asarray(frame), mask,
+                     None if filter_kernel is None else np.asarray(filter_kernel), min_area, connectivity)
+    frame = device.to_device(frame, torch.float64 if _is_f64(frame) else torch.float32)     # one upload for both steps
+    mask = None if mask is None else device.to_device(mask, torch.uint8)
+    labels, n = label(frame, threshold, mask=mask, filter_kernel=filter_kernel, min_area=min_area,
+                      connectivity=connectivity)
+    table, flags, bbox = measure(frame, labels, n, background=background, mask=mask)
+    return Sources(labels, table, flags, bbox)

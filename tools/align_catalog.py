@@ -5,10 +5,13 @@ reference's 5-image `cc.find_displacement` (align.py:656-699), for a synthetic 4
 5000-source catalog -- device-resident: the frames live on the GPU, `cutout.CutoutCatalog` describes the
 cutouts by a box table, and the whole per-source loop is four kernel launches.
 
-    python tools/align_catalog.py [--size 4096] [--sources 5000] [--dtype float32|float64]
+    python tools/align_catalog.py [--size 4096] [--sources 5000] [--dtype float32|float64] [--detect [--noise S]]
 
 --dtype float64 renders both frames in float64 and runs both catalogs in float64 (the reference's semantics for
 float64 frames: it computes in the cutouts' dtype).
+--detect finds the sources of the drizzled frame on the device (`subpixal_amd.detect.find_sources`: threshold,
+labelling, isophotal positions) instead of using the drawn segmentation and the scene's true positions; --noise S
+adds Gaussian noise of sigma S to both frames first (default with --detect: 0.002, detection threshold 5 S).
 """
 import argparse
 import os
@@ -23,7 +26,15 @@ sys.path.insert(0, os.path.join(ROOT, 'tools'))
 import align_synthetic                                      # noqa: E402  (scene + renderer)
 
 
-def build(size=4096, nsrc=5000, seed=5, margin=6, pad=3, dtype='float32'):
+DETECT_NOISE = 0.002         # the faintest source peaks at 0.5 and falls to 0.011 at its segment's edge (2.75 sigma)
+
+
+def transform(s, xy):
+    """the scene's exact drizzled -> image position map"""
+    return (xy - s['c']) @ s['f'].T + s['c'] + s['t']
+
+
+def build(size=4096, nsrc=5000, seed=5, margin=6, pad=3, dtype='float32', noise=0.0, detect=False, min_area=5):
     """Frames, segmentation, catalogs and maps (frames and catalogs in `dtype`).
 
     Sources sit on a jittered grid (no two closer than ~35 px), 98 % compact (sigma 4 px, segment = ellipse
@@ -34,7 +45,13 @@ def build(size=4096, nsrc=5000, seed=5, margin=6, pad=3, dtype='float32'):
     per source --, the image cutout of a source is the same box moved by the integer part of the displacement,
     the drizzled cutout is the box grown by `margin`, so the image-cutout -> drizzled-cutout pixel map is a pure
     offset; pixels of a drizzled cutout outside its own segment are masked and zeroed (cutout.py:190,
-    align.py:661)."""
+    align.py:661).
+
+    noise > 0 adds Gaussian noise of that sigma to both frames (its own generator: the scene does not change).
+    detect=True: the segmentation, the boxes and the source positions come from `detect.find_sources` on the
+    drizzled frame (threshold 5 * noise, or 0.01 without noise; `min_area` pixels at least) and every detected
+    position's image-frame counterpart from the scene's exact transform; boxes, maps and catalogs are then
+    derived from the detected boxes exactly as from the drawn ones."""
     import torch
     from subpixal_amd import blot, cutout
     rng = np.random.default_rng(seed)
@@ -72,28 +89,50 @@ def build(size=4096, nsrc=5000, seed=5, margin=6, pad=3, dtype='float32'):
         ix, iy = int(round(xy[k, 0])), int(round(xy[k, 1]))
         inside = (gy[:, None] / ay) ** 2 + (gx[None, :] / ax) ** 2 <= 1.0
         seg[iy - ay:iy + ay + 1, ix - ax:ix + ax + 1][inside] = k + 1
-    seg_d = torch.from_numpy(seg).cuda()
-    ids, boxes = cutout.primary_cutout_boxes(seg_d, pad=pad)            # 8f-3: one pass over the label image
-    k = ids - 1                                                          # (a segment can vanish under others)
-    shift = np.round(xy2[k] - xy[k]).astype(np.int32)
+    if noise > 0:
+        nrng = np.random.default_rng(seed + 1000)
+        drz_frame += (noise * nrng.standard_normal(drz_frame.shape)).astype(dtype)
+        img_frame += (noise * nrng.standard_normal(img_frame.shape)).astype(dtype)
+    scene = dict(f=f, t=t, c=c, xy_all=xy, big_all=big, drz_frame=drz_frame, noise=noise)
+    drz_d = torch.from_numpy(drz_frame).cuda()
+    if detect:
+        from subpixal_amd import detect as _detect
+        src = _detect.find_sources(drz_d, 5.0 * noise if noise > 0 else 0.01, min_area=min_area)
+        seg_d = src.segmentation
+        ids, boxes = cutout.primary_cutout_boxes(seg_d, pad=pad)
+        ok = (src.flags[ids - 1] & _detect.FLAG_NOFLUX) == 0
+        ids, boxes = ids[ok], boxes[ok]
+        pos = np.stack([src.x[ids - 1], src.y[ids - 1]], axis=1)
+        pos2 = transform(scene, pos)
+        weights = None
+        compact = src.npix[ids - 1] < 1500                            # (the drawn compact segments hold < 1000 px)
+        scene['src'] = src
+    else:
+        seg_d = torch.from_numpy(seg).cuda()
+        ids, boxes = cutout.primary_cutout_boxes(seg_d, pad=pad)        # 8f-3: one pass over the label image
+        k = ids - 1                                                      # (a segment can vanish under others)
+        pos, pos2 = xy[k], xy2[k]
+        weights = rng.uniform(0.5, 2.0, len(k))
+        compact = ~big[k]
+    shift = np.round(pos2 - pos).astype(np.int32)
     iboxes = boxes.copy()
     iboxes[:, :2] += shift
     dboxes = boxes + np.array([-margin, -margin, 2 * margin, 2 * margin], np.int32)
-    weights = rng.uniform(0.5, 2.0, len(k))
-    img_cat = cutout.CutoutCatalog(torch.from_numpy(img_frame).cuda(), iboxes, src_pos=xy2[k], src_id=ids,
+    img_cat = cutout.CutoutCatalog(torch.from_numpy(img_frame).cuda(), iboxes, src_pos=pos2, src_id=ids,
                                    dtype=dtype)
-    drz_cat = cutout.CutoutCatalog(torch.from_numpy(drz_frame).cuda(), dboxes, src_pos=xy[k], src_weight=weights,
+    drz_cat = cutout.CutoutCatalog(drz_d, dboxes, src_pos=pos, src_weight=weights,
                                    src_id=ids, segmentation_image=seg_d, dtype=dtype)
     img_cat._frame_host, drz_cat._frame_host = img_frame, drz_frame      # (saves the D2H copy when cutouts are built)
-    affine = blot.shift_affine(len(k), x0=(shift[:, 0] + margin).astype(np.float64),
+    affine = blot.shift_affine(len(ids), x0=(shift[:, 0] + margin).astype(np.float64),
                                y0=(shift[:, 1] + margin).astype(np.float64))
-    return dict(img_cat=img_cat, drz_cat=drz_cat, affine=affine, xy=xy[k], xy2=xy2[k], f=f, t=t, c=c, compact=~big[k])
+    return dict(img_cat=img_cat, drz_cat=drz_cat, affine=affine, xy=pos, xy2=pos2, compact=compact, **scene)
 
 
-def run(size=4096, nsrc=5000, reps=5, quiet=False, nclip=12, cc_type='NCC', dtype='float32'):
+def run(size=4096, nsrc=5000, reps=5, quiet=False, nclip=12, cc_type='NCC', dtype='float32', noise=0.0,
+        detect=False):
     import torch
     from subpixal_amd.align import find_linear_fit, iter_linear_fit
-    s = build(size, nsrc, dtype=dtype)
+    s = build(size, nsrc, dtype=dtype, noise=noise, detect=detect)
     times = []
     for _ in range(reps + 1):
         torch.cuda.synchronize()
@@ -127,5 +166,8 @@ if __name__ == '__main__':
     ap.add_argument('--size', type=int, default=4096)
     ap.add_argument('--sources', type=int, default=5000)
     ap.add_argument('--dtype', choices=('float32', 'float64'), default='float32')
+    ap.add_argument('--detect', action='store_true', help='sources from detect.find_sources, not the drawn segments')
+    ap.add_argument('--noise', type=float, default=None, help='sigma of the noise added to both frames')
     a = ap.parse_args()
-    run(a.size, a.sources, dtype=a.dtype)
+    run(a.size, a.sources, dtype=a.dtype, detect=a.detect,
+        noise=(DETECT_NOISE if a.detect else 0.0) if a.noise is None else a.noise)

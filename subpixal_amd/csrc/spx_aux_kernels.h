@@ -107,7 +107,12 @@ void gather_cutouts_kernel(const T* __restrict__ frame, const uint8_t* __restric
 //             + s [f1 + (s^2-1)/6 d2f1 + (s^2-1)(s^2-4)/120 d4f1],   t = 1 - s,
 // applied along x to six rows and then along y; samples outside the source are continued
 // by v(-k) = 2 v(0) - v(k) (and likewise at the far edge); points that map outside the
-// source give 0 (tblot's misval, blot.py:113).  Parity with drizzlepac is UNPINNED.
+// source give 0 (tblot's misval, blot.py:113).  Two statements, kept apart:
+//   parity with drizzlepac is still UNPINNED (drizzlepac is absent);
+//   agreement with the interpolant and the continuation stated here is PINNED at every edge-band position
+//   (cells 0, 1, n-4 .. n-1 per axis, the corners, the far edge itself) on 6x6 .. 13x11 sources, per pixel,
+//   against the oracle's float64 Lagrange form: tests/blot_cases.py, run by tests/test_blot_edges_cpu.py
+//   and tests/test_gpu_blot_edges.py.
 //   dither q = 00, 10, 01, 11 <-> (ox, oy) in {0, 1/2}^2: imct.dx -= 0.5 puts cutout pixel x at
 //   image position x + blc - dx0 + 1/2 (cutout.py:1138), so target pixel (x, y) samples the
 //   source at (xs, ys) = A (x + ox, y + oy) + b,  affine = (a0..a5): xs = a0 x' + a1 y' + a2.

@@ -338,17 +338,18 @@ extern "C" int emu_label_bboxes(const int32_t* seg, int fny, int fnx, int max_la
     return 0;
 }
 
+// the fixed-shape blots stride a grid of 3 workgroups over the output, or of emu_set_grid's size
 extern "C" int emu_blot_affine4(const float* src, int64_t nbatch, int sny, int snx,
                                const double* affine, const float* gain, int ny, int nx, float* im4) {
     if (sny < 6 || snx < 6) return -2;
-    rt::launch(3, 256, [&] { blot_affine4_kernel(src, nbatch, sny, snx, affine, gain, ny, nx, im4); }, 0);
+    rt::launch(g_grid > 0 ? g_grid : 3, 256, [&] { blot_affine4_kernel(src, nbatch, sny, snx, affine, gain, ny, nx, im4); }, 0);
     return 0;
 }
 
 extern "C" int emu_blot_poly4(const float* src, int64_t nbatch, int sny, int snx, const double* coef,
                               int degree, const float* gain, int ny, int nx, float* im4) {
     if (sny < 6 || snx < 6 || degree < 1 || degree > 5) return -2;
-    rt::launch(3, 256, [&] { blot_poly4_kernel(src, nbatch, sny, snx, coef, degree, gain, ny, nx, im4); }, 0);
+    rt::launch(g_grid > 0 ? g_grid : 3, 256, [&] { blot_poly4_kernel(src, nbatch, sny, snx, coef, degree, gain, ny, nx, im4); }, 0);
     return 0;
 }
 #endif   // EMU_PART 4

@@ -27,6 +27,8 @@
  *   spx_detect_label_f32 / _f64, spx_measure_labels_f32 / _f64
  *                               <-  the source finder the reference shells out to (catalogs.py:
  *                                   SExImageCatalog): segmentation image and isophotal measurements.
+ *   spx_background_mesh_f32 / _f64, spx_background_maps_f32 / _f64
+ *                               <-  the same program's background mesh: sky and noise maps, detection threshold.
  *   spx_blot_affine4_f32        <-  the four blot_cutout(dzct, imct) calls per source of
  *                                   subpixal/align.py:664-676 (blot.py:79-155, drizzlepac
  *                                   tblot, interp='poly5') for coordinate maps that are
@@ -352,6 +354,64 @@ int spx_measure_labels_f32(const float* frame, const uint8_t* bad_mask, double b
 int spx_measure_labels_f64(const double* frame, const uint8_t* bad_mask, double bkg_scalar, const double* bkg_map,
                            const int32_t* labels, int fny, int fnx, int nlabels, const int32_t* boxes,
                            double* out_table_f64, int32_t* out_flags_i32, void* stream);
+
+/*
+ * Sky background and noise maps (the background mesh SExtractor starts with; the reference gets both maps
+ * from it): frame -> per-cell sigma-clipped statistics -> median-filtered mesh -> bicubic-spline maps, and the
+ * detection threshold map spx_detect_label_* takes.  The definitions are this library's own.
+ *
+ * MESH.  Cells of bh x bw pixels; ncy = ceil(fny / bh), ncx = ceil(fnx / bw); the last cell of an axis may be
+ * partial.  8 <= bh, bw <= 128 and bh * bw <= 16384 (float64 frames: 8192), so that a cell's values fit 64 KiB
+ * of LDS: anything else is SPX_E_SHAPE.  float64 frames are processed in float64, float32 frames in float32.
+ * USABLE PIXEL: finite, bad_mask (uint8, non-zero = bad, or NULL) clear, and labels (int32 segmentation of an
+ * earlier spx_detect_label_*, or NULL) zero.
+ * PER CELL, on the n usable values sorted ascending, with the range [lo, hi) = [0, n):
+ *   1. med = median of sorted[lo:hi]; an even count takes (a + b) * 0.5 of the two middle values in float64.
+ *   2. If sorted[lo] == sorted[hi - 1] (all values equal): mean = that value, std = 0, stop.  Otherwise mean and
+ *      std (population standard deviation, two passes) in float64 with a fixed reduction order.
+ *   3. Stop if std is not > 0 or max_iters rounds are done (max_iters = 0: no clipping).
+ *   4. The new range is the part of [lo, hi) with med - kappa std <= v <= med + kappa std (contiguous in the
+ *      sorted values: two binary searches).  Stop if it equals the old range, or if it would be empty (only
+ *      possible for kappa < 1; the old range is kept); otherwise go to 1.
+ *   mesh_rms = std;  mesh_bkg = mean if std == 0, 2.5 med - 1.5 mean if |mean - med| < 0.3 std, else med;
+ *   mesh_ngood = n (the count before clipping).  A cell is BAD when n < max(2, ceil(min_good_fraction *
+ *   cell_pixels)), cell_pixels being the true pixel count of a partial cell: its mesh_bkg and mesh_rms are NaN.
+ *   SPX_E_ARG: null frame or output, kappa not positive and finite, max_iters < 0, min_good_fraction outside
+ *   0..1.  Results are bit-identical from run to run.
+ * MAPS.  A mesh cell counts as good when mesh_ngood >= 2 and neither mesh value is NaN (what
+ * spx_background_mesh_* writes; a caller may knock further cells out the same way).
+ *   Filter, for the bkg and the rms mesh alike, filter_size fs in {1, 3, 5, 7} (else SPX_E_ARG): every cell, good
+ *   or bad, takes the median of the good cells in the fs x fs window around it, truncated at the mesh border
+ *   (even count: mean of the two middle values; fs = 1: good cells keep their value).  A window without a
+ *   good cell takes the median of all good cells of the mesh.  A mesh without any good cell sets bit 0 of
+ *   `status` (int32 on the device, written by every call) and the maps are NaN.
+ *   Expansion: tensor-product natural cubic spline through the filtered mesh, knots at the uniform cell
+ *   centres cy_j = j bh + (bh - 1) / 2, cx_i = i bw + (bw - 1) / 2 (also for a partial last cell); pixel
+ *   coordinates outside [c_0, c_last] are clamped to it; one knot on an axis: constant along it, two: linear.
+ *   This is scipy.interpolate.CubicSpline(bc_type='natural') along y, then along x, evaluated in float64 and
+ *   rounded once to the maps' dtype; rms_out is clamped at 0 from below first.
+ *   thr_out = float32(double(bkg as stored) + nsigma * double(rms as stored)), the threshold frame of
+ *   spx_detect_label_*.  Each of bkg_out, rms_out, thr_out may be NULL (all three: SPX_E_ARG).
+ *   work: spx_background_workspace_bytes(fny, fnx, bh, bw) bytes (0 for sizes the calls refuse); too small or
+ *   NULL: SPX_E_WORKSPACE.  It starts with float64 planes [2][6][ncy * ncx]: plane [0][0] is the filtered
+ *   background mesh, plane [1][0] the filtered rms mesh, the others spline coefficients.
+ *   SPX_E_SHAPE: frame or box sizes as above, or ncy, ncx not ceil(fny / bh), ceil(fnx / bw).
+ */
+size_t spx_background_workspace_bytes(int fny, int fnx, int bh, int bw);
+int spx_background_mesh_f32(const float* frame, const uint8_t* bad_mask, const int32_t* labels, int fny, int fnx,
+                            int bh, int bw, double kappa, int max_iters, double min_good_fraction,
+                            double* mesh_bkg, double* mesh_rms, int32_t* mesh_ngood, void* stream);
+int spx_background_mesh_f64(const double* frame, const uint8_t* bad_mask, const int32_t* labels, int fny, int fnx,
+                            int bh, int bw, double kappa, int max_iters, double min_good_fraction,
+                            double* mesh_bkg, double* mesh_rms, int32_t* mesh_ngood, void* stream);
+int spx_background_maps_f32(const double* mesh_bkg, const double* mesh_rms, const int32_t* mesh_ngood, int ncy,
+                            int ncx, int bh, int bw, int filter_size, int fny, int fnx, double nsigma, void* work,
+                            size_t work_bytes, float* bkg_out, float* rms_out, float* thr_out, int32_t* status,
+                            void* stream);
+int spx_background_maps_f64(const double* mesh_bkg, const double* mesh_rms, const int32_t* mesh_ngood, int ncy,
+                            int ncx, int bh, int bw, int filter_size, int fny, int fnx, double nsigma, void* work,
+                            size_t work_bytes, double* bkg_out, double* rms_out, float* thr_out, int32_t* status,
+                            void* stream);
 
 /*
  * Half-pixel dithered blots: for every source the four images image00, image10, image01,

@@ -79,6 +79,16 @@ _SIGNATURES = {
                                           _vp, _vp]),
     'spx_measure_labels_f64': (_c.c_int, [_vp, _vp, _c.c_double, _vp, _vp, _c.c_int, _c.c_int, _c.c_int, _vp, _vp,
                                           _vp, _vp]),
+    # sky background: per-cell statistics (spx_background_mesh_*), filtered mesh -> maps (spx_background_maps_*)
+    'spx_background_workspace_bytes': (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    'spx_background_mesh_f32': (_c.c_int, [_vp, _vp, _vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_double,
+                                           _c.c_int, _c.c_double, _vp, _vp, _vp, _vp]),
+    'spx_background_mesh_f64': (_c.c_int, [_vp, _vp, _vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_double,
+                                           _c.c_int, _c.c_double, _vp, _vp, _vp, _vp]),
+    'spx_background_maps_f32': (_c.c_int, [_vp, _vp, _vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
+                                           _c.c_int, _c.c_double, _vp, _c.c_size_t, _vp, _vp, _vp, _vp, _vp]),
+    'spx_background_maps_f64': (_c.c_int, [_vp, _vp, _vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
+                                           _c.c_int, _c.c_double, _vp, _c.c_size_t, _vp, _vp, _vp, _vp, _vp]),
     'spx_blot_affine4_f32': (_c.c_int, [_vp, _c.c_int64, _c.c_int, _c.c_int, _vp, _vp, _c.c_int,
                                         _c.c_int, _vp, _vp]),
     'spx_blot_poly4_f32': (_c.c_int, [_vp, _c.c_int64, _c.c_int, _c.c_int, _vp, _c.c_int, _vp, _c.c_int,

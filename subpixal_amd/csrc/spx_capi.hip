@@ -9,6 +9,7 @@
 #include "spx_kernels32.h"
 #include "spx_aux_kernels.h"
 #include "spx_detect_kernels.h"
+#include "spx_background_kernels.h"
 #include "spx_tables.h"
 #include "../../include/subpixal_hip.h"
 
@@ -1190,6 +1191,144 @@ int spx_measure_labels_f64(const double* frame, const uint8_t* bad_mask, double 
                            double* out_table_f64, int32_t* out_flags_i32, void* stream) {
     return measure_labels<double>(frame, bad_mask, bkg_scalar, bkg_map, labels, fny, fnx, nlabels, boxes,
                                   out_table_f64, out_flags_i32, stream);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------
+// background and noise maps (spx_background_kernels.h).  Workspace: float64 planes [2 meshes][6][ncy * ncx]
+// (plane 0 of mesh 0 / 1 = the FILTERED background / rms mesh, which callers may read back), then a 256-byte
+// control block on a 256-byte boundary.
+// ---------------------------------------------------------------------------------------------------------
+namespace {
+struct BackgroundLayout {
+    size_t ctl, total;
+};
+BackgroundLayout background_layout(int64_t ncells) {
+    BackgroundLayout b;
+    b.ctl = ((size_t)ncells * 8 * 2 * spx::kBkgPlanes + 255) / 256 * 256;
+    b.total = b.ctl + 256;
+    return b;
+}
+int background_shape(int fny, int fnx, int bh, int bw, size_t elem) {
+    if (fny < 1 || fnx < 1 || (int64_t)fny * fnx >= 2147483647LL)
+        return fail(SPX_E_SHAPE, "the frame must hold 1 .. 2^31 - 2 pixels");
+    if (bh < spx::kBkgMinBox || bw < spx::kBkgMinBox || bh > spx::kBkgMaxBox || bw > spx::kBkgMaxBox ||
+        bh * bw > spx::bkg_max_cell_pixels(elem))
+        return fail(SPX_E_SHAPE, "mesh cells must be 8..128 pixels a side and hold at most 16384 (float64: 8192) pixels");
+    return 0;
+}
+std::mutex g_bkg_mu;
+std::set<std::pair<int, const void*>> g_bkg_lds_ok;       // (device, kernel) whose dynamic-LDS limit is raised
+
+template <typename T>
+int background_mesh(const T* frame, const uint8_t* bad, const int32_t* labels, int fny, int fnx, int bh, int bw,
+                    double kappa, int max_iters, double min_good_fraction, double* mesh_bkg, double* mesh_rms,
+                    int32_t* mesh_ngood, void* stream) {
+    if (!frame || !mesh_bkg || !mesh_rms || !mesh_ngood) return fail(SPX_E_ARG, "null pointer");
+    if (!(kappa > 0.0) || !(kappa - kappa == 0.0)) return fail(SPX_E_ARG, "kappa must be positive and finite");
+    if (max_iters < 0) return fail(SPX_E_ARG, "max_iters must not be negative");
+    if (!(min_good_fraction >= 0.0 && min_good_fraction <= 1.0))
+        return fail(SPX_E_ARG, "min_good_fraction must lie in 0..1");
+    const int rc = background_shape(fny, fnx, bh, bw, sizeof(T));
+    if (rc) return rc;
+    const int lds = (int)spx::bkg_cell_lds_bytes(sizeof(T), bh, bw);
+    auto kern = spx::bkg_cell_kernel<T>;
+    if (lds > 48 * 1024) {
+        int dev = 0;
+        SPX_HIP(hipGetDevice(&dev));
+        std::lock_guard<std::mutex> lk(g_bkg_mu);
+        const auto key = std::make_pair(dev, reinterpret_cast<const void*>(kern));
+        if (!g_bkg_lds_ok.count(key)) {
+            SPX_HIP(hipFuncSetAttribute(key.second, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(spx::kBkgRedSlots * 8 + 64 * 1024)));
+            g_bkg_lds_ok.insert(key);
+        }
+    }
+    const int64_t ncells = (int64_t)((fny + bh - 1) / bh) * ((fnx + bw - 1) / bw);
+    hipLaunchKernelGGL(kern, dim3(capped_grid(ncells, 1 << 20)), dim3(256), lds, reinterpret_cast<hipStream_t>(stream),
+                       frame, bad, labels, fny, fnx, bh, bw, kappa, max_iters, min_good_fraction, mesh_bkg, mesh_rms,
+                       mesh_ngood, (double*)nullptr);
+    SPX_HIP(hipGetLastError());
+    return 0;
+}
+
+template <typename T>
+int background_maps(const double* mesh_bkg, const double* mesh_rms, const int32_t* mesh_ngood, int ncy, int ncx,
+                    int bh, int bw, int filter_size, int fny, int fnx, double nsigma, void* work, size_t work_bytes,
+                    T* bkg_out, T* rms_out, float* thr_out, int32_t* status, void* stream) {
+    if (!mesh_bkg || !mesh_rms || !mesh_ngood || !status) return fail(SPX_E_ARG, "null pointer");
+    if (!bkg_out && !rms_out && !thr_out) return fail(SPX_E_ARG, "no output map");
+    if (filter_size != 1 && filter_size != 3 && filter_size != 5 && filter_size != 7)
+        return fail(SPX_E_ARG, "filter_size must be 1, 3, 5 or 7");
+    const int rc = background_shape(fny, fnx, bh, bw, sizeof(T));
+    if (rc) return rc;
+    if (ncy != (fny + bh - 1) / bh || ncx != (fnx + bw - 1) / bw)
+        return fail(SPX_E_SHAPE, "mesh size must be ceil(fny / bh) x ceil(fnx / bw)");
+    const int64_t nc = (int64_t)ncy * ncx;
+    const BackgroundLayout lay = background_layout(nc);
+    if (!work || work_bytes < lay.total)
+        return fail(SPX_E_WORKSPACE, "workspace missing or smaller than spx_background_workspace_bytes(fny, fnx, bh, bw)");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    double* planes = static_cast<double*>(work);
+    int32_t* ctl = reinterpret_cast<int32_t*>(static_cast<char*>(work) + lay.ctl);
+    double* fb = planes;
+    double* fr = planes + (int64_t)spx::kBkgPlanes * nc;
+    SPX_HIP(hipMemsetAsync(ctl, 0, 256, s));
+    SPX_HIP(hipMemsetAsync(status, 0, 4, s));
+    hipLaunchKernelGGL(spx::bkg_filter_kernel, dim3(capped_grid((nc + 255) / 256)), dim3(256), 0, s, mesh_bkg, mesh_rms,
+                       mesh_ngood, ncy, ncx, filter_size, fb, fr, ctl);
+    SPX_HIP(hipGetLastError());
+    hipLaunchKernelGGL(spx::bkg_global_kernel, dim3(1), dim3(256), spx::kBkgGlobalLdsBytes, s, mesh_bkg, mesh_rms,
+                       mesh_ngood, nc, fb, fr, ctl, status);
+    SPX_HIP(hipGetLastError());
+    for (int phase = 0; phase < 2; ++phase) {
+        const int64_t lines = 2 * (int64_t)(phase == 0 ? ncx + ncy : ncx);
+        hipLaunchKernelGGL(spx::bkg_spline_kernel, dim3(capped_grid((lines + 255) / 256)), dim3(256), 0, s, planes, ncy,
+                           ncx, phase);
+        SPX_HIP(hipGetLastError());
+    }
+    const int64_t groups = (int64_t)fny * ((fnx + 3) / 4);
+    hipLaunchKernelGGL(spx::bkg_expand_kernel<T>, dim3(capped_grid((groups + 255) / 256, 1 << 20)), dim3(256), 0, s,
+                       planes, ncy, ncx, bh, bw, fny, fnx, nsigma, bkg_out, rms_out, thr_out);
+    SPX_HIP(hipGetLastError());
+    return 0;
+}
+}  // namespace
+
+extern "C" {
+
+size_t spx_background_workspace_bytes(int fny, int fnx, int bh, int bw) {
+    if (fny < 1 || fnx < 1 || (int64_t)fny * fnx >= 2147483647LL) return 0;
+    if (bh < spx::kBkgMinBox || bw < spx::kBkgMinBox || bh > spx::kBkgMaxBox || bw > spx::kBkgMaxBox ||
+        bh * bw > spx::bkg_max_cell_pixels(4))
+        return 0;
+    return background_layout((int64_t)((fny + bh - 1) / bh) * ((fnx + bw - 1) / bw)).total;
+}
+int spx_background_mesh_f32(const float* frame, const uint8_t* bad_mask, const int32_t* labels, int fny, int fnx,
+                            int bh, int bw, double kappa, int max_iters, double min_good_fraction,
+                            double* mesh_bkg, double* mesh_rms, int32_t* mesh_ngood, void* stream) {
+    return background_mesh<float>(frame, bad_mask, labels, fny, fnx, bh, bw, kappa, max_iters, min_good_fraction,
+                                  mesh_bkg, mesh_rms, mesh_ngood, stream);
+}
+int spx_background_mesh_f64(const double* frame, const uint8_t* bad_mask, const int32_t* labels, int fny, int fnx,
+                            int bh, int bw, double kappa, int max_iters, double min_good_fraction,
+                            double* mesh_bkg, double* mesh_rms, int32_t* mesh_ngood, void* stream) {
+    return background_mesh<double>(frame, bad_mask, labels, fny, fnx, bh, bw, kappa, max_iters, min_good_fraction,
+                                   mesh_bkg, mesh_rms, mesh_ngood, stream);
+}
+int spx_background_maps_f32(const double* mesh_bkg, const double* mesh_rms, const int32_t* mesh_ngood, int ncy,
+                            int ncx, int bh, int bw, int filter_size, int fny, int fnx, double nsigma, void* work,
+                            size_t work_bytes, float* bkg_out, float* rms_out, float* thr_out, int32_t* status,
+                            void* stream) {
+    return background_maps<float>(mesh_bkg, mesh_rms, mesh_ngood, ncy, ncx, bh, bw, filter_size, fny, fnx, nsigma,
+                                  work, work_bytes, bkg_out, rms_out, thr_out, status, stream);
+}
+int spx_background_maps_f64(const double* mesh_bkg, const double* mesh_rms, const int32_t* mesh_ngood, int ncy,
+                            int ncx, int bh, int bw, int filter_size, int fny, int fnx, double nsigma, void* work,
+                            size_t work_bytes, double* bkg_out, double* rms_out, float* thr_out, int32_t* status,
+                            void* stream) {
+    return background_maps<double>(mesh_bkg, mesh_rms, mesh_ngood, ncy, ncx, bh, bw, filter_size, fny, fnx, nsigma,
+                                   work, work_bytes, bkg_out, rms_out, thr_out, status, stream);
 }
 
 }  // extern "C"

@@ -4,7 +4,15 @@ measurements -> the ``cutout.CutoutCatalog`` that ``align.find_linear_fit`` take
 The reference gets its segmentation image and source positions from SExtractor, an external program
 (``catalogs.py``: ``SExImageCatalog``); this module is the device-resident stand-in for that step.  Its
 definitions are its own (``include/subpixal_hip.h``, ``csrc/spx_detect_kernels.h``): parity with SExtractor is
-unpinned, and there is no deblending, background estimation or catalogue filter language here.
+unpinned, and there is no deblending or catalogue filter language here.
+
+The two inputs of detection that matter, the threshold and the background, come from the frame itself:
+:func:`estimate_background` builds the sky and noise maps on the device (sigma-clipped statistics on a mesh of
+cells, median filter, bicubic spline: ``csrc/spx_background_kernels.h``), and :func:`detect_sources` chains it
+with :func:`find_sources`::
+
+    src = detect.detect_sources(frame, nsigma=1.5, box=(64, 64), min_area=5)
+    src.background_model.background, src.background_model.rms      # CUDA tensors, the frame's shape and dtype
 """
 import numpy as np
 import torch
@@ -14,6 +22,8 @@ from . import _ffi, cutout, device
 COLUMNS = ('npix', 'flux', 'x', 'y', 'x2', 'y2', 'xy', 'a', 'b', 'theta', 'peak', 'xpeak', 'ypeak')
 FLAG_BORDER, FLAG_NOFLUX, FLAG_BADPIX = 1, 2, 4
 MAX_FILTER_SIDE = 7
+MIN_BOX, MAX_BOX = 8, 128                    # background mesh cells: sides, and pixels per cell by dtype
+MAX_CELL_PIXELS = {False: 16384, True: 8192}
 
 
 def _is_f64(frame):
@@ -177,3 +187,162 @@ def find_sources(frame, threshold, background=0.0, mask=None, filter_kernel=None
                       connectivity=connectivity)
     table, flags, bbox = measure(frame, labels, n, background=background, mask=mask)
     return Sources(labels, table, flags, bbox)
+
+
+def _check_background_arguments(frame, box, filter_size, mask, exclude, sigma, max_iters, min_good_fraction, f64):
+    """Everything :func:`estimate_background` can refuse without touching the device."""
+    if frame.ndim != 2:
+        raise ValueError("frame must be 2-D.")
+    if frame.shape[0] < 1 or frame.shape[1] < 1 or frame.shape[0] * frame.shape[1] >= 2 ** 31 - 1:
+        raise ValueError("frame must hold between 1 and 2**31 - 2 pixels.")
+    try:
+        bh, bw = box
+        ok = int(bh) == bh and int(bw) == bw
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("box must be a pair of integers (height, width).")
+    if not (MIN_BOX <= bh <= MAX_BOX and MIN_BOX <= bw <= MAX_BOX):
+        raise ValueError("box sides must lie in %d..%d." % (MIN_BOX, MAX_BOX))
+    if bh * bw > MAX_CELL_PIXELS[f64]:
+        raise ValueError("box must hold at most %d pixels for %s frames."
+                         % (MAX_CELL_PIXELS[f64], 'float64' if f64 else 'float32'))
+    if filter_size not in (1, 3, 5, 7):
+        raise ValueError("filter_size must be 1, 3, 5 or 7.")
+    if mask is not None and tuple(np.shape(mask)) != tuple(frame.shape):
+        raise ValueError("mask must have the shape of the frame.")
+    if exclude is not None:
+        if tuple(np.shape(exclude)) != tuple(frame.shape):
+            raise ValueError("exclude must have the shape of the frame.")
+        if exclude.dtype != (torch.int32 if isinstance(exclude, torch.Tensor) else np.dtype(np.int32)):
+            raise ValueError("exclude must be an int32 label image.")
+    if not (sigma > 0 and np.isfinite(sigma)):
+        raise ValueError("sigma must be positive and finite.")
+    if int(max_iters) != max_iters or max_iters < 0:
+        raise ValueError("max_iters must be an integer >= 0.")
+    if not 0.0 <= min_good_fraction <= 1.0:
+        raise ValueError("min_good_fraction must lie in 0..1.")
+
+
+class Background(object):
+    """What :func:`estimate_background` built.  ``background``, ``rms``: CUDA tensors of the frame's shape and
+    dtype.  On the mesh ``[ncy, ncx]`` (numpy): ``mesh_background``, ``mesh_rms`` AFTER the median filter (the
+    nodes the spline goes through); ``mesh_background_raw``, ``mesh_rms_raw`` BEFORE it (NaN in bad cells) and
+    ``mesh_ngood``, the usable pixels per cell before clipping.  ``box``, ``filter_size`` as given."""
+
+    def __init__(self, frame_shape, f64, box, filter_size, mesh, work, background, rms, thresholds):
+        self.box, self.filter_size = box, filter_size
+        self._shape, self._f64, self._mesh, self._work = frame_shape, f64, mesh, work
+        self.background, self.rms = background, rms
+        self._thr = thresholds
+        ncy, ncx = mesh[2].shape
+        nc = ncy * ncx
+        planes = work[:2 * 6 * nc * 8].view(torch.float64).view(2, 6, ncy, ncx)
+        self.mesh_background = planes[0, 0].cpu().numpy()
+        self.mesh_rms = planes[1, 0].cpu().numpy()
+        self.mesh_background_raw = mesh[0].cpu().numpy()
+        self.mesh_rms_raw = mesh[1].cpu().numpy()
+        self.mesh_ngood = mesh[2].cpu().numpy()
+
+    def threshold(self, nsigma):
+        """float32 CUDA tensor ``background + nsigma * rms`` (from the maps as stored), the threshold frame
+        :func:`find_sources` takes.  Evaluated on the device, once per ``nsigma``."""
+        nsigma = float(nsigma)
+        if nsigma not in self._thr:
+            thr = torch.empty(self._shape, dtype=torch.float32, device=self.background.device)
+            _background_maps(self._mesh, self.box, self.filter_size, self._shape, self._f64, self._work, nsigma,
+                             None, None, thr)
+            self._thr = {nsigma: thr}
+        return self._thr[nsigma]
+
+
+def _background_maps(mesh, box, filter_size, shape, f64, work, nsigma, bkg, rms, thr):
+    lib = _ffi.load()
+    ncy, ncx = mesh[2].shape
+    status = torch.empty((1,), dtype=torch.int32, device=work.device)
+    fn = lib.spx_background_maps_f64 if f64 else lib.spx_background_maps_f32
+    with torch.cuda.device(work.device):
+        _ffi.check(fn(device.ptr(mesh[0]), device.ptr(mesh[1]), device.ptr(mesh[2]), ncy, ncx, int(box[0]), int(box[1]),
+                      int(filter_size), int(shape[0]), int(shape[1]), float(nsigma), device.ptr(work), work.numel(),
+                      device.ptr(bkg), device.ptr(rms), device.ptr(thr), device.ptr(status), device.stream_ptr()))
+    if int(status.item()) & 1:
+        raise _ffi.SubpixalHipError("the background mesh has no good cell (too few usable pixels in every cell).")
+
+
+def _estimate_background(frame, box, filter_size, mask, exclude, sigma, max_iters, min_good_fraction, nsigma=None):
+    fshape = frame if isinstance(frame, torch.Tensor) else np.asarray(frame)
+    f64 = _is_f64(frame)
+    ex = exclude if exclude is None or isinstance(exclude, torch.Tensor) else np.asarray(exclude)
+    _check_background_arguments(fshape, box, filter_size, mask, ex, sigma, max_iters, min_good_fraction, f64)
+    tdt = torch.float64 if f64 else torch.float32
+    f = device.to_device(frame, tdt)
+    m = None if mask is None else device.to_device(mask, torch.uint8)
+    lab = None if ex is None else device.to_device(ex, torch.int32)
+    ny, nx = f.shape
+    bh, bw = int(box[0]), int(box[1])
+    ncy, ncx = -(-ny // bh), -(-nx // bw)
+    lib = _ffi.load()
+    mesh = (torch.empty((ncy, ncx), dtype=torch.float64, device=f.device),
+            torch.empty((ncy, ncx), dtype=torch.float64, device=f.device),
+            torch.empty((ncy, ncx), dtype=torch.int32, device=f.device))
+    fn = lib.spx_background_mesh_f64 if f64 else lib.spx_background_mesh_f32
+    with torch.cuda.device(f.device):
+        _ffi.check(fn(device.ptr(f), device.ptr(m), device.ptr(lab), ny, nx, bh, bw, float(sigma), int(max_iters),
+                      float(min_good_fraction), device.ptr(mesh[0]), device.ptr(mesh[1]), device.ptr(mesh[2]),
+                      device.stream_ptr()))
+    work = torch.empty((lib.spx_background_workspace_bytes(ny, nx, bh, bw),), dtype=torch.uint8, device=f.device)
+    bkg = torch.empty((ny, nx), dtype=tdt, device=f.device)
+    rms = torch.empty((ny, nx), dtype=tdt, device=f.device)
+    thr = None if nsigma is None else torch.empty((ny, nx), dtype=torch.float32, device=f.device)
+    _background_maps(mesh, (bh, bw), filter_size, (ny, nx), f64, work, 0.0 if nsigma is None else nsigma, bkg, rms,
+                     thr)
+    return Background((ny, nx), f64, (bh, bw), int(filter_size), mesh, work, bkg, rms,
+                      {} if nsigma is None else {float(nsigma): thr})
+
+
+def estimate_background(frame, box=(64, 64), filter_size=3, mask=None, exclude=None, sigma=3.0, max_iters=10,
+                        min_good_fraction=0.5):
+    """Sky background and noise maps of ``frame``, on the device (``spx_background_mesh_*`` +
+    ``spx_background_maps_*``; the definitions are in ``include/subpixal_hip.h``).
+
+    frame : 2-D numpy array or CUDA tensor; float64 frames are processed in float64, everything else in float32.
+    box : (height, width) of a mesh cell, 8..128 a side, at most 16384 pixels (float64 frames: 8192).
+    filter_size : side of the median filter over the mesh, 1, 3, 5 or 7.
+    mask : booleans ``[ny, nx]``, True = bad, or None.
+    exclude : int32 label image (a ``Sources.segmentation``): pixels with a label are left out.
+    sigma, max_iters : the clipping ``med +- sigma * std`` of each cell's values and its most rounds (0: none).
+    min_good_fraction : a cell with fewer usable pixels than this share of its pixels (or fewer than 2) is bad
+        and filled from its neighbours.
+
+    Returns a :class:`Background`; raises ``SubpixalHipError`` when no cell of the mesh is good.  All results are
+    bit-identical from run to run."""
+    return _estimate_background(frame, box, filter_size, mask, exclude, sigma, max_iters, min_good_fraction)
+
+
+def detect_sources(frame, nsigma=1.5, box=(64, 64), filter_size=3, mask=None, sigma=3.0, max_iters=10,
+                   min_good_fraction=0.5, passes=1, **find_sources_kwargs):
+    """:func:`estimate_background`, then :func:`find_sources` with ``threshold = background + nsigma * rms`` and
+    that background, without the frame leaving the device.  ``passes=2`` estimates the background again with the
+    sources of the first pass excluded and detects again.  ``find_sources_kwargs``: ``filter_kernel``,
+    ``min_area``, ``connectivity``.  Returns the :class:`Sources` with ``background_model`` attached."""
+    if passes not in (1, 2):
+        raise ValueError("passes must be 1 or 2.")
+    for k in find_sources_kwargs:
+        if k not in ('filter_kernel', 'min_area', 'connectivity'):
+            raise TypeError("detect_sources() got an unexpected keyword argument %r" % k)
+    fshape = frame if isinstance(frame, torch.Tensor) else np.asarray(frame)
+    _check_background_arguments(fshape, box, filter_size, mask, None, sigma, max_iters, min_good_fraction,
+                                _is_f64(frame))
+    _check_arguments(fshape, mask, None if find_sources_kwargs.get('filter_kernel') is None
+                     else np.asarray(find_sources_kwargs['filter_kernel']), find_sources_kwargs.get('min_area', 5),
+                     find_sources_kwargs.get('connectivity', 8))
+    frame = device.to_device(frame, torch.float64 if _is_f64(frame) else torch.float32)       # the one upload
+    mask = None if mask is None else device.to_device(mask, torch.uint8)
+    exclude, src = None, None
+    for _ in range(passes):
+        bg = _estimate_background(frame, box, filter_size, mask, exclude, sigma, max_iters, min_good_fraction,
+                                  nsigma=float(nsigma))
+        src = find_sources(frame, bg.threshold(nsigma), background=bg.background, mask=mask, **find_sources_kwargs)
+        exclude = src.segmentation
+    src.background_model = bg
+    return src

@@ -281,6 +281,11 @@ extern "C" int emu_disp5_var_f32(const float* ref, const float* im4, const int64
                                  int* status) {
     return emu_disp5_t<float>(ref, im4, nbatch, family_side, family_side, cc_type, icc, out, status, off, shp);
 }
+extern "C" int emu_disp5_var_f64(const double* ref, const double* im4, const int64_t* off, const int* shp,
+                                 int64_t nbatch, int family_side, int cc_type, float* icc, double* out,
+                                 int* status) {
+    return emu_disp5_t<double>(ref, im4, nbatch, family_side, family_side, cc_type, icc, out, status, off, shp);
+}
 
 #endif   // EMU_PART 3
 

@@ -325,6 +325,7 @@ constexpr int SCR_RED_D = 128;    // double[4*4] per-wave double partials
 constexpr int SCR_FIT = 256;      // double[25] fit box values
 constexpr int SCR_STAT = 512;     // double[8]  statistics
 constexpr int SCR_RED_D6 = 576;   // double[4*6] per-wave partials of the six-value reduction (norm_stats)
+constexpr int SCR_AHEAD = 768;    // float[4*2] per-wave sums of squares of a pair staged by its predecessor (pair_body)
 
 // ---------------------------------------------------------------------------
 // workgroup reductions
@@ -547,7 +548,9 @@ template <int C> SPX_DEVICE void load_twiddles(unsigned char* lds, const cf* __r
 // full 64x64 pair).  The value is only kept alive until the next staging, where the
 // real 16-byte loads then hit L2 instead of HBM.  (Holding the whole next pair in
 // registers does not work: hipcc spills them to scratch right after the loads, which
-// stalls the tail on HBM latency -- measured 20.3e6 vs 22.0e6 pairs/s.)
+// stalls the tail on HBM latency -- measured 20.3e6 vs 22.0e6 pairs/s.  The stage-ahead
+// path of pair_body holds them only across the refine stage, where the transform tile is
+// dead, and writes them to LDS there; this warm-up remains for the pairs that path declines.)
 SPX_DEVICE float warm_next_pair(const float* __restrict__ ref, const float* __restrict__ img) {
     const int tid = rt::thread_id();
     const float* p = (tid < 128) ? ref + tid * 32 : img + (tid - 128) * 32;
@@ -688,6 +691,44 @@ template <int C, bool FOLD> struct StageGeom {
     static SPX_DEVICE int perm(int q, int e) { return (4 * (q & 1) + e) * PS12 + (q >> 1); }
 };
 
+// Full tiles (64x64 float32, 16-byte aligned) are staged in two halves, so that a pair can be fetched while its
+// predecessor is still in its refine stage (pair_body): the ISSUE half is this thread's eight 16-byte global
+// loads (coalesced 1 KiB per wave-instruction; the image row is read back to front for the flip), the COMMIT
+// half writes them to the permuted rows and adds their squares to (sr, sm).  The commit is made of 16 pieces
+// (load i, element e), always taken in the order i-major, e-minor: the two sums are the same chain of
+// operations wherever the pieces are placed.
+struct FullTileLoads { f32x4 r[4], t[4]; };
+SPX_DEVICE void stage_full_issue(FullTileLoads& ld, const float* __restrict__ ref, const float* __restrict__ img,
+                                 int tid) {
+    const f32x4* r4 = reinterpret_cast<const f32x4*>(ref);
+    const f32x4* m4 = reinterpret_cast<const f32x4*>(img);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int idx = tid + i * kThreads;            // 1024 float4 per image
+        const int y = idx >> 4;
+        ld.r[i] = r4[idx];
+        ld.t[i] = m4[(63 - y) * 16 + (15 - (idx & 15))];
+    }
+}
+template <int C>
+SPX_DEVICE void stage_full_piece(unsigned char* lds, const FullTileLoads& ld, int i, int e, int tid,
+                                 const NormStatsT<float>& ns, float& sr, float& sm) {
+    typedef StageGeom<C, false> G;
+    float* zre = reinterpret_cast<float*>(lds + Lds<C>::R_OFF);
+    float* zim = zre + G::ROWS * G::ZS;
+    const int idx = tid + i * kThreads;
+    const int y = idx >> 4;
+    float r = ld.r[i][e], m = ld.t[i][3 - e];
+    if (ns.active) {
+        m = norm_im(m, ns);
+        r = norm_ref(r, ns);
+    }
+    zre[y * G::ZS + G::perm(idx & 15, e)] = r;
+    zim[y * G::ZS + G::perm(idx & 15, e)] = m;
+    sr += r * r;
+    sm += m * m;
+}
+
 // ssq[0] += sum ref^2, ssq[1] += sum img^2 over this thread's pixels (as staged).
 template <int C, bool FOLD = false, typename TIn = float, bool NARROW = false, bool NX4 = false>
 SPX_DEVICE void stage_pair_rows(unsigned char* lds, const TIn* __restrict__ ref,
@@ -701,32 +742,13 @@ SPX_DEVICE void stage_pair_rows(unsigned char* lds, const TIn* __restrict__ ref,
     float* zim = zre + G::ROWS * G::ZS;
     const bool aligned = ((reinterpret_cast<uintptr_t>(ref) | reinterpret_cast<uintptr_t>(img)) & 15) == 0;
     if constexpr (!FOLD && sizeof(TIn) == 4) if (ny == 64 && nx == 64 && aligned) {
-        // full tiles: 16-byte global loads (coalesced 1 KiB per wave-instruction) and
-        // 16-byte LDS stores; the image row is read back to front for the flip
-        const f32x4* r4 = reinterpret_cast<const f32x4*>(ref);
-        const f32x4* m4 = reinterpret_cast<const f32x4*>(img);
+        // full tiles: both halves back to back
+        FullTileLoads ld;
+        stage_full_issue(ld, ref, img, tid);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int idx = tid + i * kThreads;            // 1024 float4 per image
-            const int y = idx >> 4;
-            f32x4 r = r4[idx];
-            const f32x4 t = m4[(63 - y) * 16 + (15 - (idx & 15))];
-            f32x4 m = f32x4{t[3], t[2], t[1], t[0]};
-            if (ns.active) {
+        for (int i = 0; i < 4; ++i)
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    m[e] = norm_im(m[e], ns);
-                    r[e] = norm_ref(r[e], ns);
-                }
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                zre[y * G::ZS + G::perm(idx & 15, e)] = r[e];
-                zim[y * G::ZS + G::perm(idx & 15, e)] = m[e];
-                sr += r[e] * r[e];
-                sm += m[e] * m[e];
-            }
-        }
+            for (int e = 0; e < 4; ++e) stage_full_piece<C>(lds, ld, i, e, tid, ns, sr, sm);
         ssq[0] = sr;
         ssq[1] = sm;
         return;
@@ -1526,9 +1548,13 @@ SPX_DEVICE void load_rolled_tables(RolledTables<WB>& rt_, const float* __restric
             for (int r = 0; r < 4; ++r) rt_.x[b][4 * t + r] = tx[b * kBlk + 16 * (16 * t + r)];
 }
 
-template <int C, int WB>
+// `mid(k)`, k = 0..15, is called behind the k-th step of stage 2 (one block): independent work of the caller's
+// that runs in the shadow of the dependent MFMA chain and is published by the class-sum barrier below
+// (pair_body stages the next pair there).
+struct NoMidWork { SPX_DEVICE void operator()(int) const {} };
+template <int C, int WB, typename Mid = NoMidWork>
 SPX_DEVICE void fine_window_rolled(unsigned char* lds, const float (&afrag)[16][4], const RolledTables<WB>& kt,
-                                   int rot) {
+                                   int rot, Mid mid = Mid()) {
     typedef Lds<C> L;
     typedef RefineF32 R;
     typedef R::V4 V4;
@@ -1561,11 +1587,13 @@ SPX_DEVICE void fine_window_rolled(unsigned char* lds, const float (&afrag)[16][
 #pragma unroll
     for (int t = 0; t < 4; ++t)
 #pragma unroll
-        for (int r = 0; r < 4; ++r)
+        for (int r = 0; r < 4; ++r) {
 #pragma unroll
             for (int bb = 0; bb < WB; ++bb)
 #pragma unroll
                 for (int ab = 0; ab < WB; ++ab) f[bb][ab] = R::mma(kt.x[bb][4 * t + r], acc[ab][t][r], f[bb][ab]);
+            mid(4 * t + r);
+        }
     // as fine_window: one window per class (W = 16), or one shared window the classes add to in class order
     auto put = [&](int bb, int ab, const V4& fv, int c) {
 #pragma unroll
@@ -1751,20 +1779,41 @@ SPX_DEVICE void pair_body(const TIn* __restrict__ ref, const TIn* __restrict__ i
                           const float* __restrict__ ktab, double* __restrict__ out,
                           int* __restrict__ status, unsigned char* lds, PhaseClock<DBG>& clk,
                           const TIn* __restrict__ next_ref, const TIn* __restrict__ next_img,
-                          float& warm, int fit_wave, double inv_u) {
+                          float& warm, bool& staged, int fit_wave, double inv_u) {
     typedef Lds<C> L;
     ny = rt::launder_uniform(ny);
     nx = rt::launder_uniform(nx);
     U = rt::launder_uniform(U);
     const int tid = fresh_tid();
     unsigned char* scr = lds + L::SCR_OFF;
-    const NormStatsT<TIn> ns = norm_stats(scr, ref, img, 1, 0, ny, nx, cc_type);
-    float ssq[2];
-    rt::consume(warm);        // the warm-up load of this pair has landed (or was never issued)
-    stage_pair<C, FOLD, TIn>(lds, ref, img, ny, nx, ns, ssq);
-    const float bal = balance_factor(scr, ssq);       // includes the barrier after staging
+    constexpr bool kRolled = WB == 1 && R::kRolled;
+    // Stage-ahead (float32 refine, one window block, plain CC, full tiles): from the barrier of the coarse
+    // arg-max on nothing reads the class planes any more -- the A fragments are in registers, the fine windows
+    // live behind the exchange region -- so the pair stages its SUCCESSOR there during its own refine stage,
+    // in the shadow of the dependent MFMA chain, and the class-sum barrier publishes it.  `staged` (workgroup-
+    // uniform) says on entry that the predecessor did so for this pair, and on exit that this pair did.
+    constexpr bool kAhead = kRolled && !FOLD && sizeof(TIn) == 4 && (DBG == 0 || DBG == 100);
+    bool was_staged = false;
+    if constexpr (kAhead) was_staged = staged;
+    staged = false;
+    float bal;
+    if (was_staged) {
+        // same association as block_sum2f; the slots were written before the predecessor's class-sum barrier
+        // and are next written behind this pair's arg-max barrier
+        const float* part = reinterpret_cast<const float*>(scr + SCR_AHEAD);
+        const float s0 = (part[0] + part[2]) + (part[4] + part[6]);
+        const float s1 = (part[1] + part[3]) + (part[5] + part[7]);
+        bal = balance_from_ssq(s0, s1);
+        clk.tick(19);
+    } else {
+        const NormStatsT<TIn> ns = norm_stats(scr, ref, img, 1, 0, ny, nx, cc_type);
+        float ssq[2];
+        rt::consume(warm);        // the warm-up load of this pair has landed (or was never issued)
+        stage_pair<C, FOLD, TIn>(lds, ref, img, ny, nx, ns, ssq);
+        bal = balance_factor(scr, ssq);       // includes the barrier after staging
+        clk.tick(0);
+    }
     const float oscale = 0.5f / ((float)(L::P * L::P) * bal);
-    clk.tick(0);
     if constexpr (DBG == 1) return;
     const int rot = (C * C - fit_wave) & (C * C - 1);     // the fitting wave takes the lightest class (0,0)
     if (cc_planes<C, DBG, FOLD>(lds, bal, clk, rot)) return;
@@ -1777,7 +1826,6 @@ SPX_DEVICE void pair_body(const TIn* __restrict__ ref, const TIn* __restrict__ i
     // (one window block, upsample up to 11.  Two blocks were built the same way and left: the fixed order changes the
     // float32 accumulation order of the two 64-term chains, which moved sigma 11..15 px spots at upsample 27 from
     // inside to 1.13e-3 px of the float64 definition (test_gpu_r3.py); four blocks spilled 28 registers)
-    constexpr bool kRolled = WB == 1 && R::kRolled;
     FineTables<(WB > 0 ? WB : 1), R> ft;
     float afrag[kRolled ? 16 : 1][4];
     if constexpr (kRolled) load_afrag<C>(lds, afrag, rot);
@@ -1818,8 +1866,52 @@ SPX_DEVICE void pair_body(const TIn* __restrict__ ref, const TIn* __restrict__ i
                 RolledTables<(WB > 0 ? WB : 1)> kt;
                 load_rolled_tables<C, (WB > 0 ? WB : 1)>(kt, ktab, ny, nx, qyc, qxc, rot);
                 // after the tables: vmcnt counts in issue order, and the refine must not wait for a trip to HBM
-                if constexpr (sizeof(TIn) == 4) if (iter == 0 && next_ref) warm = warm_next_pair(next_ref, next_img);
-                fine_window_rolled<C, (WB > 0 ? WB : 1)>(lds, afrag, kt, rot);
+                bool ahead = false;
+                if constexpr (kAhead) ahead = iter == 0 && next_ref && cc_type == CC_PLAIN;
+                if (ahead) {
+                    // the successor's pixels instead of its warm-up: issued here, written to the staging region
+                    // piece by piece behind the steps of stage 2 (by then the loads are two thousand cycles old),
+                    // the wave's two sums of squares to SCR_AHEAD; the class-sum barrier publishes both.  (The
+                    // diagnostic build commits in one block behind the last step, between stamps of its own.)
+                    if constexpr (kAhead) {
+                        FullTileLoads nl;
+                        const int atid = fresh_tid();
+                        stage_full_issue(nl, reinterpret_cast<const float*>(next_ref),
+                                         reinterpret_cast<const float*>(next_img), atid);
+                        rt::sched_fence();      // issued HERE: left alone the scheduler sinks the loads into stage 1
+                        NormStatsT<float> nns;
+                        nns.active = 0;
+                        nns.im_mean = 0; nns.im_rstd = 1; nns.ref_mean = 0; nns.ref_rstd = 1;
+                        float sr = 0.0f, sm = 0.0f;
+                        auto finish = [&]() {
+#pragma unroll
+                            for (int m = 32; m >= 1; m >>= 1) {
+                                sr += rt::shfl_xor(sr, m);
+                                sm += rt::shfl_xor(sm, m);
+                            }
+                            float* part = reinterpret_cast<float*>(scr + SCR_AHEAD);
+                            if ((atid & 63) == 0) { part[2 * (atid >> 6)] = sr; part[2 * (atid >> 6) + 1] = sm; }
+                        };
+                        auto commit = [&](int k) {
+                            if constexpr (DBG == 100) {
+                                if (k != 15) return;
+                                clk.tick(12);
+#pragma unroll
+                                for (int j = 0; j < 16; ++j) stage_full_piece<C>(lds, nl, j >> 2, j & 3, atid, nns, sr, sm);
+                                finish();
+                                clk.tick(18);
+                            } else {
+                                stage_full_piece<C>(lds, nl, k >> 2, k & 3, atid, nns, sr, sm);
+                                if (k == 15) finish();
+                            }
+                        };
+                        fine_window_rolled<C, (WB > 0 ? WB : 1)>(lds, afrag, kt, rot, commit);
+                        staged = true;
+                    }
+                } else {
+                    if constexpr (sizeof(TIn) == 4) if (iter == 0 && next_ref) warm = warm_next_pair(next_ref, next_img);
+                    fine_window_rolled<C, (WB > 0 ? WB : 1)>(lds, afrag, kt, rot);
+                }
             } else {
                 fine_window<C, (WB > 0 ? WB : 1), R>(lds, ft, ny, nx, qyc, qxc, rot);
             }
@@ -1900,6 +1992,7 @@ SPX_TKERNEL(256) void pair_kernel(const TIn* __restrict__ ref, const TIn* __rest
         ((reinterpret_cast<uintptr_t>(ref) | reinterpret_cast<uintptr_t>(img)) & 15) == 0;
     const int64_t step = rt::grid_size();
     float warm = 0.0f;
+    bool staged = false;      // the pair about to start was staged by its predecessor (pair_body)
     // the wave that does the (serial) 5x5 fit rotates from pair to pair, and starts
     // differently in neighbouring workgroups, so that no SIMD carries it every time
     int fit_wave = (int)(rt::block_id() & 3);
@@ -1911,7 +2004,7 @@ SPX_TKERNEL(256) void pair_kernel(const TIn* __restrict__ ref, const TIn* __rest
         pair_body<C, WB, DBG, FOLD, TIn, R>(ref + p * stride, img + p * stride, ny, nx, U, cc_type, tw_g, ktab,
                               out + 2 * p, status ? status + p : nullptr, lds, clk,
                               more ? ref + (p + step) * stride : nullptr,
-                              more ? img + (p + step) * stride : nullptr, warm, fit_wave, inv_u);
+                              more ? img + (p + step) * stride : nullptr, warm, staged, fit_wave, inv_u);
         fit_wave = (fit_wave + 1) & 3;
         // upsample > 1: the last workgroup-wide step of a pair is the class sum of the fine
         // window; after it every wave only reads that window (own arg-max, wave 0's fit),

@@ -17,7 +17,11 @@ st = torch.zeros((N + 40,), dtype=torch.int32, device='cuda')
 WAVES = int(os.environ.get('WAVES', 4))        # 4: pair_kernel; 8: w8::pair8_kernel (spx_kernels8.h)
 names = ['stage+norm+balance', 'tile load (+barrier)', 'fwd A: pretw + ffts', 'fwd A: twiddle', 'transpose 1', 'fwd B ffts',
          'Z^2', 'inv A: ffts + twiddle', 'transpose 2', 'inv B ffts', 'planes write (+2 barriers)', 'coarse argmax',
-         'fine window MFMA (+class sum)', 'fine argmax', 'store', 'end barrier', 'window decision', '5x5 fit (one wave)']
+         'fine window MFMA (+class sum)', 'fine argmax', 'store', 'end barrier', 'window decision', '5x5 fit (one wave)',
+         'stage-ahead: commit next pair (in refine)', 'staged start: partials + balance']
+# Phase 0 is the staging of a pair that stages itself (the first of a walk, or a path without stage-ahead); a pair
+# staged by its predecessor has phase 19 instead, and its staging shows as phase 18 of the predecessor.  The diagnostic
+# build commits in one block behind the last stage-2 MFMA (the product interleaves it with the steps of stage 2).
 def run():
     rc = lib.spx_diag_pair_phase(ref.data_ptr(), img.data_ptr(), N, 64, 64, 100 if WAVES == 4 else 300, out.data_ptr(), st.data_ptr(),
                                  torch.cuda.current_stream().cuda_stream)

@@ -1,7 +1,9 @@
 #!/usr/bin/env python
 """Diagnostic: time the pair kernel (64x64, upsample=10) cut short after each phase.
 Needs the diagnostic library (`make -C subpixal_amd/csrc diag`), whose phase variants are
-separately compiled template instantiations (the product library carries none of them)."""
+separately compiled template instantiations (the product library carries none of them).
+The cut-short variants stage every pair themselves; only the full kernel (0) stages a pair's successor during
+its refine stage, so its delta against 13 also holds what that saves."""
 import ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -17,7 +19,7 @@ out = torch.empty((N, 2), dtype=torch.float64, device='cuda')
 st = torch.empty((N,), dtype=torch.int32, device='cuda')
 names = {1: 'stage', 2: 'fwd A ffts', 3: 'fwd A twiddle', 4: 'transpose 1', 5: 'fwd B ffts', 6: 'unpack+product',
          7: 'inv A', 8: 'transpose 2', 9: 'inv B ffts', 10: 'planes', 11: 'coarse argmax', 12: 'fine window (MFMA)',
-         13: 'fine argmax', 0: 'full (fit + store)'}
+         13: 'fine argmax', 0: 'full (fit+store, ahead)'}
 def run(k):
     rc = lib.spx_diag_pair_phase(ref.data_ptr(), img.data_ptr(), N, 64, 64, k, out.data_ptr(), st.data_ptr(),
                                  torch.cuda.current_stream().cuda_stream)

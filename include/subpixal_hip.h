@@ -356,6 +356,68 @@ int spx_measure_labels_f64(const double* frame, const uint8_t* bad_mask, double 
                            double* out_table_f64, int32_t* out_flags_i32, void* stream);
 
 /*
+ * Deblending of merged sources: a multi-threshold tree per segment of a label image and a level-by-level
+ * flood from the branches that count, in the spirit of SExtractor's DEBLEND_NTHRESH / DEBLEND_MINCONT.  The
+ * definition is this library's own (SExtractor's tree is unpinned); after two IEEE steps per pixel it is
+ * integer arithmetic throughout, so labels are bit-reproducible and independent of scheduling, grid size and
+ * of whether a parent's state lived in LDS or in the workspace.
+ *   frame, bad_mask, filter, fky, fkx, fny, fnx : as spx_detect_label_*.  f is the filtered image as defined
+ *       there (same fused multiply-add chain in the frame's dtype; v' = 0 outside the frame and at masked or
+ *       non-finite pixels; without a filter f = v'), converted exactly to float64
+ *   labels   : int32 [fny][fnx], labels 1..nlabels (others count as background)
+ *   boxes    : int32 [nlabels + 1][4], the table spx_label_bboxes_i32 writes (row = label)
+ *   nlevels  : n with n + 1 in {2, 4, 8, 16, 32, 64};  contrast : c in [0, 1];  mode : 0 exponential, 1 linear
+ * Per parent P (the pixels of one label inside its box; other labels inside the box are ignored everywhere):
+ *  1. lo = min f, hi = max f over P.  hi <= lo: the parent is left whole.
+ *     q(p) = min(2^30, floor(((f(p) - lo) / (hi - lo)) * 2^30)), an integer; float64, every operation rounded
+ *     on its own.  F(X) = sum of q over X, an exact 64-bit integer.
+ *  2. TQ_0 = 0.  Mode 0 with lo > 0 and rho = hi / lo finite: g = rho with sqrt applied log2(n + 1) times,
+ *     p_0 = 1, p_k = p_(k-1) * g, x_k = ((p_k - 1) / (rho - 1)) * 2^30, TQ_k = min(2^30, ceil(x_k)), k = 1..n.
+ *     Mode 1, and every other case of mode 0: TQ_k = k * 2^30 / (n + 1).  All float64, each step rounded on
+ *     its own, only + - * / sqrt.  S_k = {p in P : q(p) >= TQ_k}; S_0 = P.
+ *  3. Tree, k = n down to 0.  The children of a connected component C of S_k (`connectivity`) are the
+ *     components of S_(k+1) inside C.  A child D is significant when objs(D) is not empty, or when
+ *     (double)F(D) >= c * (double)F(P) and |D| >= min_area.  With two or more significant children objs(C) is
+ *     the union over the significant children of objs(D) if that is not empty, else {D}.  Otherwise objs(C) is
+ *     the (at most one) non-empty objs(D) among its children, or empty; then C as a whole goes on as one
+ *     candidate, its insignificant bumps included.  objs(P) empty: the parent is left whole.  Otherwise the
+ *     members of objs(P) are the seeds, numbered 1..m in raster order of each seed's first pixel.
+ *  4. Flood.  o(p) = the seed number on seed pixels, 0 elsewhere.  For k = n down to 0, synchronous sweeps
+ *     until one changes nothing: every p in P with o(p) = 0 and q(p) >= TQ_k that has a neighbour
+ *     (`connectivity`) with o > 0 in the PREVIOUS sweep's state takes the o of the neighbour with the largest q;
+ *     ties go to the smallest o.  All of a connected P ends up assigned (pixels of a parent that is not
+ *     connected under `connectivity` and that no seed can reach stay together as one further child).
+ *  5. Parents whose bounding box holds more than SPX_DEBLEND_MAX_BOX_PIXELS pixels are left whole and flagged.
+ *   work       : spx_deblend_workspace_bytes(fny, fnx, nlabels) bytes of device memory (0 for sizes the call
+ *                refuses); too small or NULL: SPX_E_WORKSPACE, and nothing is written
+ *   out_labels : int32 [fny][fnx] (not `labels` itself): every final segment, children and untouched parents,
+ *                numbered 1..L' in raster order of its first pixel
+ *   out_parent : int32 [max_out], row l' - 1 = the input label the segment came from
+ *   out_dflags : int32 [max_out], bit 3 (8) the segment is a child of a split parent, bit 4 (16) the parent
+ *                was over the box limit and was not examined; the values continue spx_measure_labels_*'s flags
+ *   max_out    : rows of out_parent / out_dflags; rows beyond are not written and out_nlabels still holds the
+ *                true count.  fny * fnx / min_area rows suffice for labels made with the same min_area
+ *   out_nlabels: int32 [1] on the DEVICE: L', or -1 if a union-find chain failed its consistency check
+ * SPX_E_ARG: null pointer (bad_mask and filter may be NULL), connectivity not 4 / 8, min_area < 1, nlabels or
+ * max_out < 0, nlevels + 1 not a power of two in 2..64, contrast outside [0, 1] or NaN, mode not 0 / 1, even
+ * filter side or side > 7; SPX_E_SHAPE: fny or fnx < 1, or fny * fnx >= 2^31 - 1.  All checked before any HIP call.
+ */
+#define SPX_DEBLEND_MAX_BOX_PIXELS 65536
+#define SPX_FLAG_DEBLENDED 8
+#define SPX_FLAG_NODEBLEND 16
+size_t spx_deblend_workspace_bytes(int fny, int fnx, int nlabels);
+int spx_deblend_labels_f32(const float* frame, const uint8_t* bad_mask, const float* filter, int fky, int fkx,
+                           int fny, int fnx, const int32_t* labels, int nlabels, const int32_t* boxes,
+                           int connectivity, int min_area, int nlevels, double contrast, int mode, void* work,
+                           size_t work_bytes, int32_t* out_labels, int32_t* out_parent, int32_t* out_dflags,
+                           int max_out, int32_t* out_nlabels, void* stream);
+int spx_deblend_labels_f64(const double* frame, const uint8_t* bad_mask, const double* filter, int fky, int fkx,
+                           int fny, int fnx, const int32_t* labels, int nlabels, const int32_t* boxes,
+                           int connectivity, int min_area, int nlevels, double contrast, int mode, void* work,
+                           size_t work_bytes, int32_t* out_labels, int32_t* out_parent, int32_t* out_dflags,
+                           int max_out, int32_t* out_nlabels, void* stream);
+
+/*
  * Sky background and noise maps (the background mesh SExtractor starts with; the reference gets both maps
  * from it): frame -> per-cell sigma-clipped statistics -> median-filtered mesh -> bicubic-spline maps, and the
  * detection threshold map spx_detect_label_* takes.  The definitions are this library's own.

@@ -79,6 +79,16 @@ _SIGNATURES = {
                                           _vp, _vp]),
     'spx_measure_labels_f64': (_c.c_int, [_vp, _vp, _c.c_double, _vp, _vp, _c.c_int, _c.c_int, _c.c_int, _vp, _vp,
                                           _vp, _vp]),
+    # deblending of merged sources (spx_deblend_labels_*): frame, mask, filter, fky, fkx, fny, fnx, labels,
+    # nlabels, boxes, connectivity, min_area, nlevels, contrast, mode, work, work_bytes, out_labels, out_parent,
+    # out_dflags, max_out, out_nlabels, stream
+    'spx_deblend_workspace_bytes': (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int]),
+    'spx_deblend_labels_f32': (_c.c_int, [_vp, _vp, _vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _vp, _c.c_int, _vp,
+                                          _c.c_int, _c.c_int, _c.c_int, _c.c_double, _c.c_int, _vp, _c.c_size_t,
+                                          _vp, _vp, _vp, _c.c_int, _vp, _vp]),
+    'spx_deblend_labels_f64': (_c.c_int, [_vp, _vp, _vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _vp, _c.c_int, _vp,
+                                          _c.c_int, _c.c_int, _c.c_int, _c.c_double, _c.c_int, _vp, _c.c_size_t,
+                                          _vp, _vp, _vp, _c.c_int, _vp, _vp]),
     # sky background: per-cell statistics (spx_background_mesh_*), filtered mesh -> maps (spx_background_maps_*)
     'spx_background_workspace_bytes': (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int, _c.c_int]),
     'spx_background_mesh_f32': (_c.c_int, [_vp, _vp, _vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_double,

@@ -9,6 +9,7 @@
 #include "spx_kernels32.h"
 #include "spx_aux_kernels.h"
 #include "spx_detect_kernels.h"
+#include "spx_deblend_kernels.h"
 #include "spx_background_kernels.h"
 #include "spx_tables.h"
 #include "../../include/subpixal_hip.h"
@@ -1191,6 +1192,135 @@ int spx_measure_labels_f64(const double* frame, const uint8_t* bad_mask, double 
                            double* out_table_f64, int32_t* out_flags_i32, void* stream) {
     return measure_labels<double>(frame, bad_mask, bkg_scalar, bkg_map, labels, fny, fnx, nlabels, boxes,
                                   out_table_f64, out_flags_i32, stream);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------
+// deblending (spx_deblend_kernels.h).  Workspace: the detection's layout (R | cnt | chunk sums | status) for the
+// numbering kernels, then per-parent flags int32 [nlabels + 1], then min(nlabels, kDebSlots) slots of 36 B per
+// pixel of the largest box a parent can have (min(65536, fny * fnx)) for the parents that do not fit LDS.
+// ---------------------------------------------------------------------------------------------------------
+namespace {
+struct DeblendLayout {
+    DetectLayout det;
+    size_t pflag, slots, slot_bytes, total;
+    int nslots;
+};
+DeblendLayout deblend_layout(int64_t npix, int nlabels) {
+    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+    DeblendLayout d;
+    d.det = detect_layout(npix);
+    d.pflag = d.det.total;
+    d.slots = d.pflag + up(((size_t)nlabels + 1) * 4);
+    const int64_t most = npix < spx::kDebMaxBoxPixels ? npix : spx::kDebMaxBoxPixels;
+    d.slot_bytes = most > spx::kDebLdsPixels ? up((size_t)most * spx::kDebBytesPerPixel) : 0;
+    d.nslots = nlabels < spx::kDebSlots ? nlabels : spx::kDebSlots;
+    d.total = d.slots + d.slot_bytes * (size_t)d.nslots;
+    return d;
+}
+
+template <typename T>
+int deblend_labels(const T* frame, const uint8_t* bad, const T* filter, int fky, int fkx, int fny, int fnx,
+                   const int32_t* labels, int nlabels, const int32_t* boxes, int conn, int min_area, int nlevels,
+                   double contrast, int mode, void* work, size_t work_bytes, int32_t* out_labels,
+                   int32_t* out_parent, int32_t* out_dflags, int max_out, int32_t* out_nlabels, void* stream) {
+    if (!frame || !labels || !boxes || !out_labels || !out_parent || !out_dflags || !out_nlabels)
+        return fail(SPX_E_ARG, "null pointer");
+    if (fny < 1 || fnx < 1 || (int64_t)fny * fnx >= 2147483647LL)
+        return fail(SPX_E_SHAPE, "the frame must hold 1 .. 2^31 - 2 pixels");
+    if (nlabels < 0 || max_out < 0) return fail(SPX_E_ARG, "negative label count or max_out");
+    if (conn != 4 && conn != 8) return fail(SPX_E_ARG, "connectivity must be 4 or 8");
+    if (min_area < 1) return fail(SPX_E_ARG, "min_area must be at least 1");
+    if (nlevels < 1 || nlevels > 63 || ((nlevels + 1) & nlevels))
+        return fail(SPX_E_ARG, "nlevels + 1 must be a power of two in 2..64");
+    if (!(contrast >= 0.0 && contrast <= 1.0)) return fail(SPX_E_ARG, "contrast must lie in 0..1");
+    if (mode != 0 && mode != 1) return fail(SPX_E_ARG, "mode must be 0 (exponential) or 1 (linear)");
+    if (!filter) fky = fkx = 1;
+    if (fky < 1 || fkx < 1 || !(fky & 1) || !(fkx & 1) || fky > spx::kDetMaxFilter || fkx > spx::kDetMaxFilter)
+        return fail(SPX_E_ARG, "filter sides must be odd and at most 7");
+    const int npix = fny * fnx;
+    const DeblendLayout lay = deblend_layout(npix, nlabels);
+    if (!work || work_bytes < lay.total)
+        return fail(SPX_E_WORKSPACE, "workspace missing or smaller than spx_deblend_workspace_bytes(fny, fnx, nlabels)");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    char* w = static_cast<char*>(work);
+    int32_t* R = reinterpret_cast<int32_t*>(w + lay.det.r);
+    int32_t* cnt = reinterpret_cast<int32_t*>(w + lay.det.cnt);
+    int32_t* sums = reinterpret_cast<int32_t*>(w + lay.det.sums);
+    int32_t* status = reinterpret_cast<int32_t*>(w + lay.det.status);
+    int32_t* pflag = reinterpret_cast<int32_t*>(w + lay.pflag);
+    unsigned char* slots = reinterpret_cast<unsigned char*>(w + lay.slots);
+    SPX_HIP(hipMemsetAsync(status, 0, 4, s));
+    SPX_HIP(hipMemsetAsync(R, 0, (size_t)npix * 4, s));
+    SPX_HIP(hipMemsetAsync(pflag, 0, ((size_t)nlabels + 1) * 4, s));
+    if (nlabels > 0) {
+        // one launch per storage class, each over all labels (a workgroup skips the other classes' parents)
+        hipLaunchKernelGGL((spx::deblend_parents_kernel<T, 64, false>), dim3(capped_grid(nlabels, 1 << 20)), dim3(64),
+                           spx::deb_lds_bytes(spx::kDebWavePixels), s, frame, bad, filter, fky, fkx, fny, fnx, labels,
+                           nlabels, boxes, conn, min_area, nlevels, contrast, mode, 0, spx::kDebWavePixels, slots,
+                           lay.slot_bytes, R, cnt, pflag, status);
+        SPX_HIP(hipGetLastError());
+        const int mid[3] = {spx::kDebWavePixels, spx::kDebMidPixels, spx::kDebLdsPixels};
+        for (int c = 0; c < 2 && npix > mid[c]; ++c) {
+            hipLaunchKernelGGL((spx::deblend_parents_kernel<T, 256, false>), dim3(capped_grid(nlabels, 1 << 20)),
+                               dim3(256), spx::deb_lds_bytes(mid[c + 1]), s, frame, bad, filter, fky, fkx, fny, fnx,
+                               labels, nlabels, boxes, conn, min_area, nlevels, contrast, mode, mid[c] + 1, mid[c + 1],
+                               slots, lay.slot_bytes, R, cnt, pflag, status);
+            SPX_HIP(hipGetLastError());
+        }
+        if (npix > spx::kDebLdsPixels) {
+            hipLaunchKernelGGL((spx::deblend_parents_kernel<T, spx::kDebWsThreads, true>), dim3((unsigned)lay.nslots),
+                               dim3(spx::kDebWsThreads), spx::deb_lds_bytes(0), s, frame, bad, filter, fky, fkx, fny, fnx,
+                               labels, nlabels, boxes, conn, min_area, nlevels, contrast, mode, spx::kDebLdsPixels + 1,
+                               spx::kDebMaxBoxPixels, slots, lay.slot_bytes, R, cnt, pflag, status);
+            SPX_HIP(hipGetLastError());
+        }
+    }
+    // number the final segments as detect_label numbers components: every segment has cnt[first pixel] = 1
+    const int64_t nchunks = ((int64_t)npix + spx::kDetChunk - 1) / spx::kDetChunk;
+    hipLaunchKernelGGL(spx::detect_flag_count_kernel, dim3(capped_grid(nchunks)), dim3(256), spx::kDetScanLdsBytes,
+                       s, R, cnt, npix, 1, sums);
+    SPX_HIP(hipGetLastError());
+    hipLaunchKernelGGL(spx::detect_scan_blocks_kernel, dim3(1), dim3(256), spx::kDetScanLdsBytes, s, sums, nchunks,
+                       status, out_nlabels);
+    SPX_HIP(hipGetLastError());
+    hipLaunchKernelGGL(spx::detect_assign_kernel, dim3(capped_grid(nchunks)), dim3(256), spx::kDetScanLdsBytes, s,
+                       R, cnt, npix, 1, sums);
+    SPX_HIP(hipGetLastError());
+    hipLaunchKernelGGL(spx::detect_relabel_kernel, dim3(capped_grid(((int64_t)npix + 255) / 256)), dim3(256), 0, s,
+                       R, cnt, npix, out_labels);
+    SPX_HIP(hipGetLastError());
+    hipLaunchKernelGGL(spx::deblend_table_kernel, dim3(capped_grid(((int64_t)npix + 255) / 256)), dim3(256), 0, s, R,
+                       cnt, labels, pflag, npix, nlabels, max_out, out_parent, out_dflags);
+    SPX_HIP(hipGetLastError());
+    return 0;
+}
+}  // namespace
+
+extern "C" {
+
+size_t spx_deblend_workspace_bytes(int fny, int fnx, int nlabels) {
+    if (fny < 1 || fnx < 1 || (int64_t)fny * fnx >= 2147483647LL || nlabels < 0) return 0;
+    return deblend_layout((int64_t)fny * fnx, nlabels).total;
+}
+int spx_deblend_labels_f32(const float* frame, const uint8_t* bad_mask, const float* filter, int fky, int fkx,
+                           int fny, int fnx, const int32_t* labels, int nlabels, const int32_t* boxes,
+                           int connectivity, int min_area, int nlevels, double contrast, int mode, void* work,
+                           size_t work_bytes, int32_t* out_labels, int32_t* out_parent, int32_t* out_dflags,
+                           int max_out, int32_t* out_nlabels, void* stream) {
+    return deblend_labels<float>(frame, bad_mask, filter, fky, fkx, fny, fnx, labels, nlabels, boxes, connectivity,
+                                 min_area, nlevels, contrast, mode, work, work_bytes, out_labels, out_parent,
+                                 out_dflags, max_out, out_nlabels, stream);
+}
+int spx_deblend_labels_f64(const double* frame, const uint8_t* bad_mask, const double* filter, int fky, int fkx,
+                           int fny, int fnx, const int32_t* labels, int nlabels, const int32_t* boxes,
+                           int connectivity, int min_area, int nlevels, double contrast, int mode, void* work,
+                           size_t work_bytes, int32_t* out_labels, int32_t* out_parent, int32_t* out_dflags,
+                           int max_out, int32_t* out_nlabels, void* stream) {
+    return deblend_labels<double>(frame, bad_mask, filter, fky, fkx, fny, fnx, labels, nlabels, boxes, connectivity,
+                                  min_area, nlevels, contrast, mode, work, work_bytes, out_labels, out_parent,
+                                  out_dflags, max_out, out_nlabels, stream);
 }
 
 }  // extern "C"

@@ -46,6 +46,15 @@ constexpr size_t det_tile_lds_bytes(size_t elem, int fky, int fkx) {
 SPX_DEVICE float det_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 SPX_DEVICE double det_fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
 
+// the filter sum of the DEFINITIONS at one pixel; v(j, i) = v' at row j, column i of the kernel's footprint
+template <typename T, typename V>
+SPX_DEVICE T det_filter_chain(const T* fk, int fky, int fkx, V v) {
+    T f = T(0);
+    for (int j = 0; j < fky; ++j)
+        for (int k = 0; k < fkx; ++k) f = det_fma(fk[j * fkx + k], v(j, k), f);
+    return f;
+}
+
 SPX_DEVICE int det_find(const int32_t* L, int p, int& err) {
     for (int it = 0; it < kDetMaxChain; ++it) {
         const int q = rt::atomic_load_i32(L + p) - 1;
@@ -117,9 +126,7 @@ void detect_tile_kernel(const T* __restrict__ frame, const uint8_t* __restrict__
             if (!lab[i]) continue;
             T f;
             if (filt) {
-                f = T(0);
-                for (int j = 0; j < fky; ++j)
-                    for (int k = 0; k < fkx; ++k) f = det_fma(fk[j * fkx + k], fr[(ly + j) * frw + lx + k], f);
+                f = det_filter_chain<T>(fk, fky, fkx, [&](int j, int k) { return fr[(ly + j) * frw + lx + k]; });
             } else {
                 f = fr[(ly + hy) * frw + lx + hx];
             }

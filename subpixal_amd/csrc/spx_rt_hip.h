@@ -98,6 +98,9 @@ SPX_DEVICE int atomic_min_ret_i32(int* p, int v) { return atomicMin(p, v); }
 SPX_DEVICE int atomic_load_i32(const int* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
+// for spx_deblend_kernels.h (LDS or global): exact integer flux sums per component, flag bits per root
+SPX_DEVICE void atomic_accum_u64(unsigned long long* p, unsigned long long v) { atomicAdd(p, v); }
+SPX_DEVICE void atomic_or_i32(int* p, int v) { atomicOr(p, v); }
 
 // ---------------------------------------------------------------------------
 // Packed complex arithmetic on (re, im) register pairs: one VOP3P instruction each,

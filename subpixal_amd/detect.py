@@ -4,7 +4,9 @@ measurements -> the ``cutout.CutoutCatalog`` that ``align.find_linear_fit`` take
 The reference gets its segmentation image and source positions from SExtractor, an external program
 (``catalogs.py``: ``SExImageCatalog``); this module is the device-resident stand-in for that step.  Its
 definitions are its own (``include/subpixal_hip.h``, ``csrc/spx_detect_kernels.h``): parity with SExtractor is
-unpinned, and there is no deblending or catalogue filter language here.
+unpinned, and there is no catalogue filter language here.  Merged sources are split on request
+(:func:`deblend`, ``find_sources(..., deblend=True)``: a multi-threshold tree and a flood per segment,
+``csrc/spx_deblend_kernels.h``).
 
 The two inputs of detection that matter, the threshold and the background, come from the frame itself:
 :func:`estimate_background` builds the sky and noise maps on the device (sigma-clipped statistics on a mesh of
@@ -21,6 +23,8 @@ from . import _ffi, cutout, device
 
 COLUMNS = ('npix', 'flux', 'x', 'y', 'x2', 'y2', 'xy', 'a', 'b', 'theta', 'peak', 'xpeak', 'ypeak')
 FLAG_BORDER, FLAG_NOFLUX, FLAG_BADPIX = 1, 2, 4
+FLAG_DEBLENDED, FLAG_NODEBLEND = 8, 16       # a child of a split parent; a parent over the box limit, not examined
+DEBLEND_MODES = {'exponential': 0, 'linear': 1}
 MAX_FILTER_SIDE = 7
 MIN_BOX, MAX_BOX = 8, 128                    # background mesh cells: sides, and pixels per cell by dtype
 MAX_CELL_PIXELS = {False: 16384, True: 8192}
@@ -61,16 +65,28 @@ def _check_arguments(frame, mask, filter_kernel, min_area, connectivity):
             raise ValueError("filter_kernel sides must be at most %d." % MAX_FILTER_SIDE)
 
 
+def _check_deblend_arguments(levels, contrast, mode):
+    if int(levels) != levels or levels + 1 not in (2, 4, 8, 16, 32, 64):
+        raise ValueError("deblending levels must be 1, 3, 7, 15, 31 or 63 (levels + 1 a power of two).")
+    if not 0.0 <= contrast <= 1.0:
+        raise ValueError("deblending contrast must lie in 0..1.")
+    if mode not in DEBLEND_MODES:
+        raise ValueError("deblending mode must be 'exponential' or 'linear'.")
+
+
 class Sources(object):
     """What :func:`find_sources` found.  ``segmentation``: int32 CUDA tensor ``[ny, nx]`` with labels
     ``1..len(self)`` in raster order of each segment's first pixel.  Per source (numpy, index = label - 1):
     ``id``, ``x``, ``y`` (0-based pixel centres, the convention of ``CutoutCatalog.src_pos``), ``flux``,
     ``npix``, central moments ``x2, y2, xy``, ellipse ``a, b, theta`` (degrees), ``peak`` at ``xpeak, ypeak``,
-    ``flags`` (``FLAG_BORDER | FLAG_NOFLUX | FLAG_BADPIX``) and ``bbox`` = (xmin, ymin, xmax, ymax) inclusive.
+    ``flags`` (``FLAG_BORDER | FLAG_NOFLUX | FLAG_BADPIX``, with deblending also ``FLAG_DEBLENDED |
+    FLAG_NODEBLEND``) and ``bbox`` = (xmin, ymin, xmax, ymax) inclusive.  ``parent``: with deblending, the number
+    the source's segment had BEFORE deblending (children of one merged detection share it), else ``None``.
     ``table_device`` / ``flags_device`` are the same numbers as CUDA tensors."""
 
-    def __init__(self, segmentation, table, flags, bbox):
+    def __init__(self, segmentation, table, flags, bbox, parent=None):
         self.segmentation = segmentation
+        self.parent = None if parent is None else parent.cpu().numpy()
         self.table_device, self.flags_device = table, flags
         t = table.cpu().numpy()
         for i, c in enumerate(COLUMNS):
@@ -88,6 +104,8 @@ class Sources(object):
                'semi-major-b': self.b}
         for c in ('npix', 'x2', 'y2', 'xy', 'theta', 'peak', 'xpeak', 'ypeak', 'flags'):
             out[c] = getattr(self, c)
+        if self.parent is not None:
+            out['parent'] = self.parent
         return out
 
     def cutout_catalog(self, frame, pad=1, dtype=np.float32, weight=None, mask=None):
@@ -163,7 +181,72 @@ def measure(frame, labels, nlabels, background=0.0, mask=None):
     return table, flags, boxes[1:]
 
 
-def find_sources(frame, threshold, background=0.0, mask=None, filter_kernel=None, min_area=5, connectivity=8):
+def deblend(frame, labels, nlabels, mask=None, filter_kernel=None, levels=31, contrast=0.005, mode='exponential',
+            min_area=5, connectivity=8):
+    """Split the merged sources of a label image (``spx_label_bboxes_i32`` + ``spx_deblend_labels_f32/_f64``; the
+    definition is in ``include/subpixal_hip.h``): per segment, a tree of its connected components above ``levels``
+    thresholds between its faintest and brightest (filtered) pixel, spaced exponentially or linearly; a branch
+    counts when it holds at least ``contrast`` of the segment's quantised flux and ``min_area`` pixels; a segment
+    with two or more such branches is divided among them by a flood that descends level by level.
+
+    frame, mask, filter_kernel, min_area, connectivity : as given to :func:`label` for ``labels``.
+    labels, nlabels : the segmentation (int32, labels ``1..nlabels``).
+
+    Returns CUDA tensors ``(labels int32 [ny, nx], nlabels, parent int32 [nlabels], dflags int32 [nlabels])``:
+    every final segment numbered in raster order of its first pixel, the input label it came from, and
+    ``FLAG_DEBLENDED`` / ``FLAG_NODEBLEND`` (a box of more than 65536 pixels is not examined).  Bit-identical
+    from run to run.
+
+    Memory: every call allocates its scratch anew, ``spx_deblend_workspace_bytes(ny, nx, nlabels)`` bytes: 8 bytes
+    per frame pixel for the numbering, plus ``min(nlabels, 64)`` slots of 36 bytes per pixel of the largest box a
+    parent may have (``min(65536, ny * nx)``) for the parents that do not fit LDS -- about 150 MB for any frame of
+    65536 pixels or more with 64 labels or more, whether or not a parent comes near that size."""
+    fshape = frame if isinstance(frame, torch.Tensor) else np.asarray(frame)
+    kern = None if filter_kernel is None else np.asarray(filter_kernel)
+    _check_arguments(fshape, mask, kern, min_area, connectivity)
+    _check_deblend_arguments(levels, contrast, mode)
+    if tuple(np.shape(labels)) != tuple(fshape.shape):
+        raise ValueError("labels must have the shape of the frame.")
+    if int(nlabels) != nlabels or nlabels < 0:
+        raise ValueError("nlabels must be an integer >= 0.")
+    f64 = _is_f64(frame)
+    tdt = torch.float64 if f64 else torch.float32
+    f = device.to_device(frame, tdt)
+    seg = device.to_device(labels, torch.int32)
+    m = None if mask is None else device.to_device(mask, torch.uint8)
+    k = None if kern is None else device.to_device(kern, tdt)
+    fky, fkx = (1, 1) if kern is None else kern.shape
+    ny, nx = f.shape
+    nlabels = int(nlabels)
+    boxes, _ = cutout.segment_bounding_boxes(seg, max_label=nlabels)
+    lib = _ffi.load()
+    nbytes = lib.spx_deblend_workspace_bytes(ny, nx, nlabels)
+    work = torch.empty((nbytes,), dtype=torch.uint8, device=f.device)
+    out = torch.empty((ny, nx), dtype=torch.int32, device=f.device)
+    nout = torch.empty((1,), dtype=torch.int32, device=f.device)
+    fn = lib.spx_deblend_labels_f64 if f64 else lib.spx_deblend_labels_f32
+    max_out = min(ny * nx, 2 * nlabels + 1024)       # a guess; the call reports the true count, so a miss is seen
+    while True:
+        table = torch.empty((2, max_out), dtype=torch.int32, device=f.device)
+        with torch.cuda.device(f.device):
+            _ffi.check(fn(device.ptr(f), device.ptr(m), device.ptr(k), int(fky), int(fkx), ny, nx, device.ptr(seg),
+                          nlabels, device.ptr(boxes), int(connectivity), int(min_area), int(levels), float(contrast),
+                          DEBLEND_MODES[mode], device.ptr(work), nbytes, device.ptr(out), device.ptr(table[0]),
+                          device.ptr(table[1]), max_out, device.ptr(nout), device.stream_ptr()))
+        n = int(nout.item())
+        if n <= max_out:
+            break
+        max_out = n                                  # rows beyond max_out were not written: once more, with room
+    if n < 0:
+        raise _ffi.SubpixalHipError("component merge failed its consistency check (spx_deblend_labels).")
+    return out, n, table[0, :n], table[1, :n]
+
+
+_deblend = deblend           # find_sources has a keyword of the same name
+
+
+def find_sources(frame, threshold, background=0.0, mask=None, filter_kernel=None, min_area=5, connectivity=8,
+                 deblend=False, deblend_levels=31, deblend_contrast=0.005, deblend_mode='exponential'):
     """Detect, label and measure the sources of ``frame`` on the device.
 
     frame : 2-D numpy array or CUDA tensor; float64 frames are processed in float64, everything else in float32.
@@ -177,16 +260,29 @@ def find_sources(frame, threshold, background=0.0, mask=None, filter_kernel=None
         weights are not renormalised there.
     min_area : components with fewer pixels are dropped.  connectivity : 8 or 4.
 
+    deblend : split merged sources (:func:`deblend` with ``deblend_levels``, ``deblend_contrast``,
+        ``deblend_mode``) between labelling and measuring: the measurements are those of the deblended segments,
+        ``Sources.parent`` holds each one's segment number before deblending and ``flags`` gains
+        ``FLAG_DEBLENDED`` / ``FLAG_NODEBLEND``.  Off by default; nothing changes then.
+
     Returns a :class:`Sources`.  Labels are numbered in raster order of each component's first pixel, as
     ``scipy.ndimage.label`` numbers them; all results are bit-identical from run to run."""
     _check_arguments(frame if isinstance(frame, torch.Tensor) else np.asarray(frame), mask,
                      None if filter_kernel is None else np.asarray(filter_kernel), min_area, connectivity)
+    if deblend:
+        _check_deblend_arguments(deblend_levels, deblend_contrast, deblend_mode)
     frame = device.to_device(frame, torch.float64 if _is_f64(frame) else torch.float32)     # one upload for both steps
     mask = None if mask is None else device.to_device(mask, torch.uint8)
     labels, n = label(frame, threshold, mask=mask, filter_kernel=filter_kernel, min_area=min_area,
                       connectivity=connectivity)
+    if not deblend:
+        table, flags, bbox = measure(frame, labels, n, background=background, mask=mask)
+        return Sources(labels, table, flags, bbox)
+    labels, n, parent, dflags = _deblend(frame, labels, n, mask=mask, filter_kernel=filter_kernel, levels=deblend_levels,
+                                         contrast=deblend_contrast, mode=deblend_mode, min_area=min_area,
+                                         connectivity=connectivity)
     table, flags, bbox = measure(frame, labels, n, background=background, mask=mask)
-    return Sources(labels, table, flags, bbox)
+    return Sources(labels, table, flags | dflags, bbox, parent=parent)
 
 
 def _check_background_arguments(frame, box, filter_size, mask, exclude, sigma, max_iters, min_good_fraction, f64):
@@ -324,11 +420,13 @@ def detect_sources(frame, nsigma=1.5, box=(64, 64), filter_size=3, mask=None, si
     """:func:`estimate_background`, then :func:`find_sources` with ``threshold = background + nsigma * rms`` and
     that background, without the frame leaving the device.  ``passes=2`` estimates the background again with the
     sources of the first pass excluded and detects again.  ``find_sources_kwargs``: ``filter_kernel``,
-    ``min_area``, ``connectivity``.  Returns the :class:`Sources` with ``background_model`` attached."""
+    ``min_area``, ``connectivity``, ``deblend``, ``deblend_levels``, ``deblend_contrast``, ``deblend_mode``.
+    Returns the :class:`Sources` with ``background_model`` attached."""
     if passes not in (1, 2):
         raise ValueError("passes must be 1 or 2.")
     for k in find_sources_kwargs:
-        if k not in ('filter_kernel', 'min_area', 'connectivity'):
+        if k not in ('filter_kernel', 'min_area', 'connectivity', 'deblend', 'deblend_levels', 'deblend_contrast',
+                     'deblend_mode'):
             raise TypeError("detect_sources() got an unexpected keyword argument %r" % k)
     fshape = frame if isinstance(frame, torch.Tensor) else np.asarray(frame)
     _check_background_arguments(fshape, box, filter_size, mask, None, sigma, max_iters, min_good_fraction,
@@ -336,6 +434,10 @@ def detect_sources(frame, nsigma=1.5, box=(64, 64), filter_size=3, mask=None, si
     _check_arguments(fshape, mask, None if find_sources_kwargs.get('filter_kernel') is None
                      else np.asarray(find_sources_kwargs['filter_kernel']), find_sources_kwargs.get('min_area', 5),
                      find_sources_kwargs.get('connectivity', 8))
+    if find_sources_kwargs.get('deblend', False):
+        _check_deblend_arguments(find_sources_kwargs.get('deblend_levels', 31),
+                                 find_sources_kwargs.get('deblend_contrast', 0.005),
+                                 find_sources_kwargs.get('deblend_mode', 'exponential'))
     frame = device.to_device(frame, torch.float64 if _is_f64(frame) else torch.float32)       # the one upload
     mask = None if mask is None else device.to_device(mask, torch.uint8)
     exclude, src = None, None

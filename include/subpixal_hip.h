@@ -27,6 +27,9 @@
  *   spx_detect_label_f32 / _f64, spx_measure_labels_f32 / _f64
  *                               <-  the source finder the reference shells out to (catalogs.py:
  *                                   SExImageCatalog): segmentation image and isophotal measurements.
+ *   spx_measure_errors_f32 / _f64
+ *                               <-  the same catalogue's FLUXERR_ISO and FWHM_IMAGE columns (catalogs.py:75-93),
+ *                                   from which pos_std and the fit weights derive (catalogs.py:405-428, 968-987).
  *   spx_background_mesh_f32 / _f64, spx_background_maps_f32 / _f64
  *                               <-  the same program's background mesh: sky and noise maps, detection threshold.
  *   spx_blot_affine4_f32        <-  the four blot_cutout(dzct, imct) calls per source of
@@ -354,6 +357,47 @@ int spx_measure_labels_f32(const float* frame, const uint8_t* bad_mask, double b
 int spx_measure_labels_f64(const double* frame, const uint8_t* bad_mask, double bkg_scalar, const double* bkg_map,
                            const int32_t* labels, int fny, int fnx, int nlabels, const int32_t* boxes,
                            double* out_table_f64, int32_t* out_flags_i32, void* stream);
+
+/*
+ * Per-source error measurements of labels 1..nlabels: flux error, the covariance of the flux-weighted centre
+ * and a FWHM, the columns the reference's catalogue carries beside the positions (catalogs.py: fluxerr, fwhm ->
+ * pos_std -> weight) and align.find_linear_fit(use_weights=True) fits with.
+ *   frame, bad_mask, bkg_scalar, bkg_map, labels, fny, fnx, nlabels, boxes : as given to spx_measure_labels_*
+ *   table_f64 : the table spx_measure_labels_* wrote for the same labels; flux, x, y and peak are taken from its
+ *               row, so both calls agree on them to the bit
+ *   rms_map   : the noise per pixel in the frame's dtype (spx_background_maps_*'s rms), or NULL: rms_scalar
+ *   gain      : electrons per data unit; > 0 and finite adds the source's own Poisson noise, else none
+ * A pixel p of label l inside its box is usable when v_p is finite, p is not masked and labels[p] == l.  Over
+ * the usable pixels, in float64:
+ *     w_p  = v_p - bkg_p
+ *     s_p  = rms at p; an s_p that is not finite or < 0 counts as 0 and raises SPX_EFLAG_NOISE
+ *     v2_p = s_p * s_p + (w_p / gain if gain > 0 and finite and w_p > 0, else 0)
+ *   out_errors_f64 : float64 [nlabels][SPX_ERROR_COLUMNS], row l - 1 = (fluxerr, errx2, erry2, errxy, nhalf, fwhm)
+ *     fluxerr = sqrt(sum v2_p)                                 (SExtractor's FLUXERR_ISO, restated)
+ *     errx2 = sum(v2_p ux^2) / flux^2, erry2 = sum(v2_p uy^2) / flux^2, errxy = sum(v2_p ux uy) / flux^2 with
+ *             ux = x_p - x, uy = y_p - y: the first-order variance of the flux-weighted centre, since
+ *             d x / d I_p = (x_p - x) / flux; all three NaN unless the table's flux is > 0 and finite
+ *     nhalf = the number of usable pixels with w_p >= 0.5 peak (an exact count; 0 unless peak > 0)
+ *     fwhm  = 2 sqrt(nhalf / pi), the diameter of the circle whose area is the half-maximum area (NaN unless
+ *             peak > 0)
+ *   out_eflags_i32 : int32 [nlabels], values that continue spx_measure_labels_*'s flags: SPX_EFLAG_HALFMAX when
+ *             the label has usable pixels and all of them lie above half maximum (nhalf == npix: fwhm is a lower
+ *             bound), SPX_EFLAG_NOISE as above
+ * All sums are float64 in a fixed order: results are bit-identical from run to run and independent of the grid.
+ * SPX_E_ARG: nlabels < 0, or a null frame, labels, boxes, table or output; SPX_E_SHAPE: fny or fnx < 1, or
+ * fny * fnx >= 2^31 - 1; both before any HIP call.  nlabels == 0 succeeds and writes nothing.
+ */
+#define SPX_ERROR_COLUMNS 6
+#define SPX_EFLAG_HALFMAX 32
+#define SPX_EFLAG_NOISE 64
+int spx_measure_errors_f32(const float* frame, const uint8_t* bad_mask, double bkg_scalar, const float* bkg_map,
+                           double rms_scalar, const float* rms_map, double gain, const int32_t* labels, int fny,
+                           int fnx, int nlabels, const int32_t* boxes, const double* table_f64,
+                           double* out_errors_f64, int32_t* out_eflags_i32, void* stream);
+int spx_measure_errors_f64(const double* frame, const uint8_t* bad_mask, double bkg_scalar, const double* bkg_map,
+                           double rms_scalar, const double* rms_map, double gain, const int32_t* labels, int fny,
+                           int fnx, int nlabels, const int32_t* boxes, const double* table_f64,
+                           double* out_errors_f64, int32_t* out_eflags_i32, void* stream);
 
 /*
  * Deblending of merged sources: a multi-threshold tree per segment of a label image and a level-by-level

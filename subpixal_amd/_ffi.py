@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get('SPX_HIP_LIB') or os.path.join(_HERE, 'csrc', 'libsubp
 
 ABI_VERSION = 4
 MEASURE_COLUMNS = 13                                     # SPX_MEASURE_COLUMNS
+ERROR_COLUMNS = 6                                        # SPX_ERROR_COLUMNS
 REFINE_DEFAULT, REFINE_F64, REFINE_F32 = 0, 1, 2         # SPX_REFINE_* (include/subpixal_hip.h)
 MAX_SIDE = 682
 MAX_UPSAMPLE = 59
@@ -79,6 +80,12 @@ _SIGNATURES = {
                                           _vp, _vp]),
     'spx_measure_labels_f64': (_c.c_int, [_vp, _vp, _c.c_double, _vp, _vp, _c.c_int, _c.c_int, _c.c_int, _vp, _vp,
                                           _vp, _vp]),
+    # per-source errors (spx_measure_errors_*): frame, mask, bkg, bkg_map, rms, rms_map, gain, labels, fny, fnx,
+    # nlabels, boxes, the measure table, out_errors, out_eflags, stream
+    'spx_measure_errors_f32': (_c.c_int, [_vp, _vp, _c.c_double, _vp, _c.c_double, _vp, _c.c_double, _vp, _c.c_int,
+                                          _c.c_int, _c.c_int, _vp, _vp, _vp, _vp, _vp]),
+    'spx_measure_errors_f64': (_c.c_int, [_vp, _vp, _c.c_double, _vp, _c.c_double, _vp, _c.c_double, _vp, _c.c_int,
+                                          _c.c_int, _c.c_int, _vp, _vp, _vp, _vp, _vp]),
     # deblending of merged sources (spx_deblend_labels_*): frame, mask, filter, fky, fkx, fny, fnx, labels,
     # nlabels, boxes, connectivity, min_area, nlevels, contrast, mode, work, work_bytes, out_labels, out_parent,
     # out_dflags, max_out, out_nlabels, stream

@@ -9,6 +9,7 @@
 #include "spx_kernels32.h"
 #include "spx_aux_kernels.h"
 #include "spx_detect_kernels.h"
+#include "spx_error_kernels.h"
 #include "spx_deblend_kernels.h"
 #include "spx_background_kernels.h"
 #include "spx_tables.h"
@@ -1159,10 +1160,40 @@ int measure_labels(const T* frame, const uint8_t* bad, double bkg_scalar, const 
     SPX_HIP(hipGetLastError());
     return 0;
 }
+
+template <typename T>
+int measure_errors(const T* frame, const uint8_t* bad, double bkg_scalar, const T* bkg_map, double rms_scalar,
+                   const T* rms_map, double gain, const int32_t* labels, int fny, int fnx, int nlabels,
+                   const int32_t* boxes, const double* table, double* out, int32_t* out_flags, void* stream) {
+    if (nlabels < 0) return fail(SPX_E_ARG, "negative label count");
+    if (fny < 1 || fnx < 1 || (int64_t)fny * fnx >= 2147483647LL)
+        return fail(SPX_E_SHAPE, "the frame must hold 1 .. 2^31 - 2 pixels");
+    if (nlabels == 0) return 0;
+    if (!frame || !labels || !boxes || !table || !out || !out_flags) return fail(SPX_E_ARG, "null pointer");
+    hipLaunchKernelGGL(spx::measure_errors_kernel<T>, dim3(capped_grid(nlabels, 1 << 20)), dim3(256),
+                       spx::kErrorLdsBytes, reinterpret_cast<hipStream_t>(stream), frame, bad, bkg_scalar, bkg_map,
+                       rms_scalar, rms_map, gain, labels, fny, fnx, nlabels, boxes, table, out, out_flags);
+    SPX_HIP(hipGetLastError());
+    return 0;
+}
 }  // namespace
 
 extern "C" {
 
+int spx_measure_errors_f32(const float* frame, const uint8_t* bad_mask, double bkg_scalar, const float* bkg_map,
+                           double rms_scalar, const float* rms_map, double gain, const int32_t* labels, int fny,
+                           int fnx, int nlabels, const int32_t* boxes, const double* table_f64,
+                           double* out_errors_f64, int32_t* out_eflags_i32, void* stream) {
+    return measure_errors<float>(frame, bad_mask, bkg_scalar, bkg_map, rms_scalar, rms_map, gain, labels, fny, fnx,
+                                 nlabels, boxes, table_f64, out_errors_f64, out_eflags_i32, stream);
+}
+int spx_measure_errors_f64(const double* frame, const uint8_t* bad_mask, double bkg_scalar, const double* bkg_map,
+                           double rms_scalar, const double* rms_map, double gain, const int32_t* labels, int fny,
+                           int fnx, int nlabels, const int32_t* boxes, const double* table_f64,
+                           double* out_errors_f64, int32_t* out_eflags_i32, void* stream) {
+    return measure_errors<double>(frame, bad_mask, bkg_scalar, bkg_map, rms_scalar, rms_map, gain, labels, fny, fnx,
+                                  nlabels, boxes, table_f64, out_errors_f64, out_eflags_i32, stream);
+}
 size_t spx_detect_workspace_bytes(int fny, int fnx) {
     if (fny < 1 || fnx < 1 || (int64_t)fny * fnx >= 2147483647LL) return 0;
     return detect_layout((int64_t)fny * fnx).total;

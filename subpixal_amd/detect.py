@@ -4,9 +4,11 @@ measurements -> the ``cutout.CutoutCatalog`` that ``align.find_linear_fit`` take
 The reference gets its segmentation image and source positions from SExtractor, an external program
 (``catalogs.py``: ``SExImageCatalog``); this module is the device-resident stand-in for that step.  Its
 definitions are its own (``include/subpixal_hip.h``, ``csrc/spx_detect_kernels.h``): parity with SExtractor is
-unpinned, and there is no catalogue filter language here.  Merged sources are split on request
-(:func:`deblend`, ``find_sources(..., deblend=True)``: a multi-threshold tree and a flood per segment,
-``csrc/spx_deblend_kernels.h``).
+unpinned.  Merged sources are split on request (:func:`deblend`, ``find_sources(..., deblend=True)``: a
+multi-threshold tree and a flood per segment, ``csrc/spx_deblend_kernels.h``).  With a noise map the sources also
+get a flux error, a FWHM and from them the reference's ``pos_std`` and fit ``weight`` (:func:`measure_errors`,
+``find_sources(..., rms=...)``, ``detect_sources(..., errors=True)``: ``csrc/spx_error_kernels.h``); the
+catalogue filter language lives in :mod:`subpixal_amd.catalogs`.
 
 The two inputs of detection that matter, the threshold and the background, come from the frame itself:
 :func:`estimate_background` builds the sky and noise maps on the device (sigma-clipped statistics on a mesh of
@@ -24,6 +26,9 @@ from . import _ffi, cutout, device
 COLUMNS = ('npix', 'flux', 'x', 'y', 'x2', 'y2', 'xy', 'a', 'b', 'theta', 'peak', 'xpeak', 'ypeak')
 FLAG_BORDER, FLAG_NOFLUX, FLAG_BADPIX = 1, 2, 4
 FLAG_DEBLENDED, FLAG_NODEBLEND = 8, 16       # a child of a split parent; a parent over the box limit, not examined
+FLAG_HALFMAX, FLAG_NOISE = 32, 64             # every usable pixel above half maximum (fwhm is a lower bound); bad rms
+ERROR_COLUMNS = ('fluxerr', 'errx2', 'erry2', 'errxy', 'nhalf', 'fwhm')
+FWHM2SIGMA = 2.0 * np.sqrt(2.0 * np.log(2.0))         # the reference's _FWHM2SIGMA (catalogs.py:31)
 DEBLEND_MODES = {'exponential': 0, 'linear': 1}
 MAX_FILTER_SIDE = 7
 MIN_BOX, MAX_BOX = 8, 128                    # background mesh cells: sides, and pixels per cell by dtype
@@ -82,9 +87,16 @@ class Sources(object):
     ``flags`` (``FLAG_BORDER | FLAG_NOFLUX | FLAG_BADPIX``, with deblending also ``FLAG_DEBLENDED |
     FLAG_NODEBLEND``) and ``bbox`` = (xmin, ymin, xmax, ymax) inclusive.  ``parent``: with deblending, the number
     the source's segment had BEFORE deblending (children of one merged detection share it), else ``None``.
-    ``table_device`` / ``flags_device`` are the same numbers as CUDA tensors."""
+    ``table_device`` / ``flags_device`` are the same numbers as CUDA tensors.
 
-    def __init__(self, segmentation, table, flags, bbox, parent=None):
+    When errors were measured (``find_sources(..., rms=...)``; ``has_errors``): ``fluxerr``, the centre's
+    covariance ``errx2, erry2, errxy``, ``nhalf`` and ``fwhm`` from :func:`measure_errors` (``errors_device`` is the
+    CUDA tensor), and on the host ``snr = flux / fluxerr``, ``pos_std = fwhm / (2 sqrt(2 ln 2) snr)`` and ``weight =
+    1 / pos_std**2`` by the reference's formulas (catalogs.py:405-428, 968-987); ``flags`` then also carries
+    ``FLAG_HALFMAX | FLAG_NOISE``.  Without them none of these attributes exists."""
+    has_errors = False
+
+    def __init__(self, segmentation, table, flags, bbox, parent=None, errors=None):
         self.segmentation = segmentation
         self.parent = None if parent is None else parent.cpu().numpy()
         self.table_device, self.flags_device = table, flags
@@ -94,6 +106,16 @@ class Sources(object):
         self.flags = flags.cpu().numpy()
         self.bbox = bbox.cpu().numpy()
         self.id = np.arange(1, len(self.flags) + 1, dtype=np.int32)
+        if errors is not None:
+            self.has_errors = True
+            self.errors_device = errors
+            e = errors.cpu().numpy()
+            for i, c in enumerate(ERROR_COLUMNS):
+                setattr(self, c, e[:, i].astype(np.int32) if c == 'nhalf' else e[:, i].copy())
+            with np.errstate(all='ignore'):
+                self.snr = self.flux / self.fluxerr
+                self.pos_std = position_std(self.fwhm, self.flux, self.fluxerr)
+                self.weight = 1.0 / self.pos_std ** 2
 
     def __len__(self):
         return len(self.id)
@@ -106,23 +128,47 @@ class Sources(object):
             out[c] = getattr(self, c)
         if self.parent is not None:
             out['parent'] = self.parent
+        if self.has_errors:
+            for c in ERROR_COLUMNS + ('snr', 'pos_std', 'weight'):
+                out[c] = getattr(self, c)
         return out
 
     def cutout_catalog(self, frame, pad=1, dtype=np.float32, weight=None, mask=None):
         """The primary cutouts of ``frame`` as a :class:`cutout.CutoutCatalog`, by the reference's rules
         (``cutout.primary_cutout_boxes``: segments touching the border are skipped, box = bounding rectangle +
         ``pad``), with ``src_pos = (x, y)``, ``src_id`` and this segmentation.  ``weight=None``: no source weights
-        (what the reference's ``compute_weights`` amounts to for equal weights); ``weight='flux'``: the fluxes.
-        Sources without a position (``FLAG_NOFLUX``) are left out."""
-        if weight not in (None, 'flux'):
-            raise ValueError("weight must be None or 'flux'.")
+        (what the reference's ``compute_weights`` amounts to for equal weights); ``weight='flux'``: the fluxes;
+        ``weight='pos_std'``: the ``weight`` column, ``1 / pos_std**2`` (what ``SExImageCatalog.compute_weights``
+        gives; needs measured errors).  Sources without a position (``FLAG_NOFLUX``) are left out, and with
+        ``weight='pos_std'`` so are sources whose weight is not finite or not positive."""
+        return self._cutout_catalog(frame, pad, dtype, weight, mask, None)
+
+    def _cutout_catalog(self, frame, pad, dtype, weight, mask, select):
+        if weight not in (None, 'flux', 'pos_std'):
+            raise ValueError("weight must be None, 'flux' or 'pos_std'.")
+        if weight == 'pos_std' and not self.has_errors:
+            raise ValueError("weight='pos_std' needs measured errors: find_sources(..., rms=...) or "
+                             "detect_sources(..., errors=True).")
         ids, boxes = cutout.primary_cutout_boxes(self.segmentation, pad=pad)
         keep = (self.flags[ids - 1] & FLAG_NOFLUX) == 0
+        if weight == 'pos_std':
+            wt = self.weight[ids - 1]
+            keep &= np.isfinite(wt) & (wt > 0)
+        if select is not None:
+            keep &= np.isin(ids, select)
         ids, boxes = ids[keep], boxes[keep]
         k = ids - 1
+        src_weight = None if weight is None else (self.flux[k] if weight == 'flux' else self.weight[k])
         return cutout.CutoutCatalog(frame, boxes, src_pos=np.stack([self.x[k], self.y[k]], axis=1),
-                                    src_weight=None if weight is None else self.flux[k], src_id=ids, mask=mask,
+                                    src_weight=src_weight, src_id=ids, mask=mask,
                                     segmentation_image=self.segmentation, dtype=dtype)
+
+
+def position_std(fwhm, flux, fluxerr):
+    """The reference's position error estimate (catalogs.py:405-428): ``fwhm / (2 sqrt(2 ln 2) * flux / fluxerr)``,
+    written with its operations in its order."""
+    with np.errstate(all='ignore'):
+        return np.asarray(fwhm / (FWHM2SIGMA * flux / fluxerr))
 
 
 def label(frame, threshold, mask=None, filter_kernel=None, min_area=5, connectivity=8):
@@ -155,7 +201,7 @@ def label(frame, threshold, mask=None, filter_kernel=None, min_area=5, connectiv
     return labels, n
 
 
-def measure(frame, labels, nlabels, background=0.0, mask=None):
+def measure(frame, labels, nlabels, background=0.0, mask=None, _all_boxes=False):
     """Isophotal measurements of labels ``1..nlabels`` (``spx_label_bboxes_i32`` + ``spx_measure_labels_f32/_f64``).
     Returns CUDA tensors ``(table float64 [nlabels, 13] in COLUMNS order, flags int32 [nlabels], bbox int32
     [nlabels, 4])``."""
@@ -178,7 +224,63 @@ def measure(frame, labels, nlabels, background=0.0, mask=None):
         _ffi.check(fn(device.ptr(f), device.ptr(m), bkg, device.ptr(bkg_map), device.ptr(seg), f.shape[0],
                       f.shape[1], int(nlabels), device.ptr(boxes), device.ptr(table), device.ptr(flags),
                       device.stream_ptr()))
-    return table, flags, boxes[1:]
+    return table, flags, (boxes if _all_boxes else boxes[1:])          # (_all_boxes: with row 0, as the C entries take it)
+
+
+def _check_error_arguments(rms, gain, shape):
+    if rms is None:
+        raise ValueError("rms must be a scalar or a frame, not None.")
+    if (isinstance(rms, torch.Tensor) or np.ndim(rms) > 0) and tuple(np.shape(rms)) != tuple(shape):
+        raise ValueError("rms must be a scalar or have the shape of the frame.")
+    if gain is not None and not (np.ndim(gain) == 0 and float(gain) > 0 and np.isfinite(float(gain))):
+        raise ValueError("gain must be None or a positive, finite scalar.")
+
+
+def measure_errors(frame, labels, nlabels, table, rms, background=0.0, gain=None, mask=None, _boxes=None):
+    """Error measurements of labels ``1..nlabels`` (``spx_label_bboxes_i32`` + ``spx_measure_errors_f32/_f64``; the
+    definitions are in ``include/subpixal_hip.h``).
+
+    frame, labels, nlabels, background, mask : as given to :func:`measure`.
+    table : the table :func:`measure` returned for them (flux, x, y and peak are taken from it).
+    rms : the noise per pixel, a scalar or a frame (used in the frame's dtype): ``Background.rms``.
+    gain : electrons per data unit; adds the source's own Poisson noise ``w / gain`` where ``w > 0``.  None: none.
+
+    Returns CUDA tensors ``(errors float64 [nlabels, 6] in ERROR_COLUMNS order, eflags int32 [nlabels])`` with
+    ``FLAG_HALFMAX`` / ``FLAG_NOISE``.  Bit-identical from run to run."""
+    shape = tuple(np.shape(frame))
+    if len(shape) != 2 or tuple(np.shape(labels)) != shape:
+        raise ValueError("frame must be 2-D and labels must have its shape.")
+    if mask is not None and tuple(np.shape(mask)) != shape:
+        raise ValueError("mask must have the shape of the frame.")
+    if int(nlabels) != nlabels or nlabels < 0:
+        raise ValueError("nlabels must be an integer >= 0.")
+    nlabels = int(nlabels)
+    _check_error_arguments(rms, gain, shape)
+    if np.ndim(background) > 0 and tuple(np.shape(background)) != shape:
+        raise ValueError("background must be a scalar or have the shape of the frame.")
+    if tuple(np.shape(table)) != (nlabels, len(COLUMNS)):
+        raise ValueError("table must be the [nlabels, %d] table of measure()." % len(COLUMNS))
+    f64 = _is_f64(frame)
+    tdt = torch.float64 if f64 else torch.float32
+    f = device.to_device(frame, tdt)
+    seg = device.to_device(labels, torch.int32)
+    bkg, bkg_map = _frame_or_scalar(background, f.shape, tdt, 'background')
+    sig, sig_map = _frame_or_scalar(rms, f.shape, tdt, 'rms')
+    m = None if mask is None else device.to_device(mask, torch.uint8)
+    tab = device.to_device(table, torch.float64)
+    boxes = _boxes                                   # (find_sources hands over the table measure() made)
+    if boxes is None:
+        boxes, _ = cutout.segment_bounding_boxes(seg, max_label=nlabels)
+    errors = torch.empty((nlabels, len(ERROR_COLUMNS)), dtype=torch.float64, device=f.device)
+    eflags = torch.empty((nlabels,), dtype=torch.int32, device=f.device)
+    lib = _ffi.load()
+    fn = lib.spx_measure_errors_f64 if f64 else lib.spx_measure_errors_f32
+    with torch.cuda.device(f.device):
+        _ffi.check(fn(device.ptr(f), device.ptr(m), bkg, device.ptr(bkg_map), sig, device.ptr(sig_map),
+                      0.0 if gain is None else float(gain), device.ptr(seg), f.shape[0], f.shape[1], nlabels,
+                      device.ptr(boxes), device.ptr(tab), device.ptr(errors), device.ptr(eflags),
+                      device.stream_ptr()))
+    return errors, eflags
 
 
 def deblend(frame, labels, nlabels, mask=None, filter_kernel=None, levels=31, contrast=0.005, mode='exponential',
@@ -246,7 +348,8 @@ _deblend = deblend           # find_sources has a keyword of the same name
 
 
 def find_sources(frame, threshold, background=0.0, mask=None, filter_kernel=None, min_area=5, connectivity=8,
-                 deblend=False, deblend_levels=31, deblend_contrast=0.005, deblend_mode='exponential'):
+                 deblend=False, deblend_levels=31, deblend_contrast=0.005, deblend_mode='exponential', rms=None,
+                 gain=None):
     """Detect, label and measure the sources of ``frame`` on the device.
 
     frame : 2-D numpy array or CUDA tensor; float64 frames are processed in float64, everything else in float32.
@@ -265,24 +368,41 @@ def find_sources(frame, threshold, background=0.0, mask=None, filter_kernel=None
         ``Sources.parent`` holds each one's segment number before deblending and ``flags`` gains
         ``FLAG_DEBLENDED`` / ``FLAG_NODEBLEND``.  Off by default; nothing changes then.
 
+    rms : the noise per pixel, a scalar or a frame (``Background.rms``).  Given, the sources are also measured by
+        :func:`measure_errors` (with ``gain``, electrons per data unit, for the sources' own Poisson noise):
+        :class:`Sources` gains ``fluxerr, errx2, erry2, errxy, nhalf, fwhm, snr, pos_std, weight`` and ``flags`` gains
+        ``FLAG_HALFMAX`` / ``FLAG_NOISE``.  None (the default): nothing changes.
+
     Returns a :class:`Sources`.  Labels are numbered in raster order of each component's first pixel, as
     ``scipy.ndimage.label`` numbers them; all results are bit-identical from run to run."""
     _check_arguments(frame if isinstance(frame, torch.Tensor) else np.asarray(frame), mask,
                      None if filter_kernel is None else np.asarray(filter_kernel), min_area, connectivity)
     if deblend:
         _check_deblend_arguments(deblend_levels, deblend_contrast, deblend_mode)
+    if rms is not None:
+        _check_error_arguments(rms, gain, np.shape(frame))
+    elif gain is not None:
+        raise ValueError("gain needs rms: errors are measured only with a noise map.")
     frame = device.to_device(frame, torch.float64 if _is_f64(frame) else torch.float32)     # one upload for both steps
     mask = None if mask is None else device.to_device(mask, torch.uint8)
     labels, n = label(frame, threshold, mask=mask, filter_kernel=filter_kernel, min_area=min_area,
                       connectivity=connectivity)
+    parent = None
     if not deblend:
-        table, flags, bbox = measure(frame, labels, n, background=background, mask=mask)
-        return Sources(labels, table, flags, bbox)
-    labels, n, parent, dflags = _deblend(frame, labels, n, mask=mask, filter_kernel=filter_kernel, levels=deblend_levels,
-                                         contrast=deblend_contrast, mode=deblend_mode, min_area=min_area,
-                                         connectivity=connectivity)
-    table, flags, bbox = measure(frame, labels, n, background=background, mask=mask)
-    return Sources(labels, table, flags | dflags, bbox, parent=parent)
+        table, flags, boxes = measure(frame, labels, n, background=background, mask=mask, _all_boxes=True)
+        if rms is None:
+            return Sources(labels, table, flags, boxes[1:])
+    else:
+        labels, n, parent, dflags = _deblend(frame, labels, n, mask=mask, filter_kernel=filter_kernel,
+                                             levels=deblend_levels, contrast=deblend_contrast, mode=deblend_mode,
+                                             min_area=min_area, connectivity=connectivity)
+        table, flags, boxes = measure(frame, labels, n, background=background, mask=mask, _all_boxes=True)
+        flags = flags | dflags
+        if rms is None:
+            return Sources(labels, table, flags, boxes[1:], parent=parent)
+    errors, eflags = measure_errors(frame, labels, n, table, rms, background=background, gain=gain, mask=mask,
+                                    _boxes=boxes)
+    return Sources(labels, table, flags | eflags, boxes[1:], parent=parent, errors=errors)
 
 
 def _check_background_arguments(frame, box, filter_size, mask, exclude, sigma, max_iters, min_good_fraction, f64):
@@ -416,14 +536,20 @@ def estimate_background(frame, box=(64, 64), filter_size=3, mask=None, exclude=N
 
 
 def detect_sources(frame, nsigma=1.5, box=(64, 64), filter_size=3, mask=None, sigma=3.0, max_iters=10,
-                   min_good_fraction=0.5, passes=1, **find_sources_kwargs):
+                   min_good_fraction=0.5, passes=1, errors=False, gain=None, **find_sources_kwargs):
     """:func:`estimate_background`, then :func:`find_sources` with ``threshold = background + nsigma * rms`` and
     that background, without the frame leaving the device.  ``passes=2`` estimates the background again with the
     sources of the first pass excluded and detects again.  ``find_sources_kwargs``: ``filter_kernel``,
     ``min_area``, ``connectivity``, ``deblend``, ``deblend_levels``, ``deblend_contrast``, ``deblend_mode``.
+    ``errors=True`` also measures the errors of the final pass's sources with its ``Background.rms`` and ``gain``
+    (``find_sources(..., rms=bg.rms, gain=gain)``); off by default, nothing changes then.
     Returns the :class:`Sources` with ``background_model`` attached."""
     if passes not in (1, 2):
         raise ValueError("passes must be 1 or 2.")
+    if errors:
+        _check_error_arguments(0.0, gain, ())
+    elif gain is not None:
+        raise ValueError("gain needs errors=True.")
     for k in find_sources_kwargs:
         if k not in ('filter_kernel', 'min_area', 'connectivity', 'deblend', 'deblend_levels', 'deblend_contrast',
                      'deblend_mode'):
@@ -441,10 +567,12 @@ def detect_sources(frame, nsigma=1.5, box=(64, 64), filter_size=3, mask=None, si
     frame = device.to_device(frame, torch.float64 if _is_f64(frame) else torch.float32)       # the one upload
     mask = None if mask is None else device.to_device(mask, torch.uint8)
     exclude, src = None, None
-    for _ in range(passes):
+    for i in range(passes):
         bg = _estimate_background(frame, box, filter_size, mask, exclude, sigma, max_iters, min_good_fraction,
                                   nsigma=float(nsigma))
-        src = find_sources(frame, bg.threshold(nsigma), background=bg.background, mask=mask, **find_sources_kwargs)
+        last = errors and i == passes - 1
+        src = find_sources(frame, bg.threshold(nsigma), background=bg.background, mask=mask,
+                           rms=bg.rms if last else None, gain=gain if last else None, **find_sources_kwargs)
         exclude = src.segmentation
     src.background_model = bg
     return src

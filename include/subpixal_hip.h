@@ -32,6 +32,9 @@
  *                                   from which pos_std and the fit weights derive (catalogs.py:405-428, 968-987).
  *   spx_background_mesh_f32 / _f64, spx_background_maps_f32 / _f64
  *                               <-  the same program's background mesh: sky and noise maps, detection threshold.
+ *   spx_drizzle_rows, spx_drizzle_f32 / _f64
+ *                               <-  Resample.execute / fast_replace_image (resample.py:535-625): the drizzle of
+ *                                   the dithered frames, for affine maps; parity with drizzlepac UNPINNED.
  *   spx_blot_affine4_f32        <-  the four blot_cutout(dzct, imct) calls per source of
  *                                   subpixal/align.py:664-676 (blot.py:79-155, drizzlepac
  *                                   tblot, interp='poly5') for coordinate maps that are
@@ -608,6 +611,78 @@ int spx_find_displacement5_catalog_f64(const double* ref, const double* im4, con
                                        int cc_type, double* out_dxdy, int32_t* out_status,
                                        float* out_icc, void* workspace, size_t workspace_bytes,
                                        void* stream);
+
+/*
+ * Drizzle: the forward resampler of dithered frames onto one output grid, for affine maps (what the reference's
+ * resample.py gets from drizzlepac; drizzlepac is not in the reference tree, so parity with it is UNPINNED.  The
+ * definition is this library's own, after Fruchter & Hook 2002, PASP 114, 144; tests/drizzle_statement.py restates
+ * it in numpy as a scatter and the kernel is pinned against that).
+ *
+ * DEFINITION
+ *   Coordinates: pixels are 0-based, pixel (i, j) has its centre at integer coordinates and covers
+ *   [i - 1/2, i + 1/2] x [j - 1/2, j + 1/2] (the blot's convention).
+ *   Inputs, for frames k = 0 .. K-1 (1 <= K <= 128): data D_k [ny_k][nx_k], all frames in one dtype (float32 or
+ *   float64), shapes may differ; an optional weight map W_k >= 0 of the same dtype (none: weight 1); an optional
+ *   uint8 bad-pixel mask; a forward affine map from input to output pixels,
+ *       (X, Y) = (a0 x + a1 y + a2, a3 x + a4 y + a5),  float64 [6]  (the layout of blot.shift_affine)
+ *   with det A != 0 (a negative determinant, a mirrored frame, is allowed); an `active` flag.
+ *   An input pixel has effective weight 0 when it is masked, its value is not finite, its weight is not finite, or
+ *   its weight is <= 0.
+ *   Drop: the drop of pixel (i, j) is the square of side pixfrac p in (0, 1] centred on it.
+ *   kernel 0 'square': Q is the parallelogram M_k(drop); a = area(Q n P_XY) / (|det A| p^2), the fraction of the
+ *                      drop that lands on output pixel P_XY.
+ *   kernel 1 'turbo' : Q is replaced by the axis-aligned square of side p sqrt|det A| centred on M_k(i, j); a is the
+ *                      overlap over that square's area.
+ *   kernel 2 'point' : a = 1 for the pixel (floor(X + 1/2), floor(Y + 1/2)) that holds M_k(i, j), 0 elsewhere.
+ *   An overlap area below 1e-12 output pixels^2 counts as 0 (rounding noise of a drop that only touches the pixel).
+ *   Accumulation: num = sum a w d and wht = sum a w over active frames in ascending k, then j ascending, then i
+ *   ascending; everything float64 with contraction off.  sci = num / wht where wht > 0, else `fill`; sci is written
+ *   in the frame dtype, wht as float32.  ctx is int32 planes [ceil(K / 32)][NY][NX]: bit k % 32 of plane k / 32 is
+ *   set iff frame k added a w > 0 to that pixel.
+ *   sci is a weighted mean of input values, i.e. input-pixel surface brightness: NO scale^2 is applied.
+ *   Geometry is float64 throughout.  Frames and the output hold fewer than 2^31 - 1 pixels each.
+ *   The result does not depend on scheduling or the grid: one thread owns one output pixel and sums in the order
+ *   above (a gather; there are no atomics).
+ *
+ * Two steps.  spx_drizzle_rows is a HOST function: it checks the frames' description and packs one row of
+ * SPX_DRIZZLE_ROW_BYTES per frame (pointers, shape, flag, the map, its inverse, the candidate window and the drop's
+ * edge vectors and slopes, all computed once in float64) into out_rows, a HOST buffer of
+ * nframes * SPX_DRIZZLE_ROW_BYTES.  The caller copies the rows to the device and keeps them there; changing one
+ * frame's map or flag rewrites one row.  spx_drizzle_f32 / _f64 take that DEVICE table and only launch, so they
+ * can be captured and never copy behind the caller's back.
+ *
+ * spx_drizzle_rows -- every array is a HOST array; the pointers inside frames / weights / masks are device pointers
+ *   frames   : [nframes] frame pointers (none may be NULL)
+ *   weights  : [nframes] weight-map pointers; the table or single entries may be NULL (weight 1)
+ *   masks    : [nframes] uint8 mask pointers; the table or single entries may be NULL
+ *   shapes   : int32 [nframes][2] = (ny, nx)
+ *   maps_f64 : float64 [nframes][6]
+ *   active   : uint8 [nframes], or NULL: every frame is active
+ *   pixfrac, kernel (SPX_DRIZZLE_SQUARE / _TURBO / _POINT), out_ny, out_nx: as above; rows depend on pixfrac and
+ *   kernel, so pass the same kernel to spx_drizzle_*
+ *   SPX_E_ARG: nframes outside 1 .. 128, pixfrac outside (0, 1] or not finite, unknown kernel, a null table or frame,
+ *   a map with an entry that is not finite, a singular map.  SPX_E_SHAPE: a frame or the output with a side < 1 or
+ *   2^31 - 1 pixels or more; a map under which one output pixel would gather from more than 8 x 8 input pixels
+ *   (2 rx + 1 > 8 for the window's half-side rx: at pixfrac 1 a frame shrunk more than sixfold).  On an error nothing is written.
+ *
+ * spx_drizzle_f32 / _f64
+ *   rows     : the DEVICE copy of what spx_drizzle_rows packed, [nframes] rows
+ *   fill     : sci where no drop lands
+ *   out_sci  : [out_ny][out_nx] in the frame dtype;  out_wht : float32 [out_ny][out_nx]
+ *   out_ctx  : int32 [ceil(nframes / 32)][out_ny][out_nx]
+ *   SPX_E_ARG: nframes, kernel, null pointer; SPX_E_SHAPE: output size.  Checked before any HIP call.
+ */
+#define SPX_DRIZZLE_ROW_BYTES 224
+#define SPX_DRIZZLE_SQUARE 0
+#define SPX_DRIZZLE_TURBO 1
+#define SPX_DRIZZLE_POINT 2
+int spx_drizzle_rows(const void* const* frames, const void* const* weights, const uint8_t* const* masks,
+                     const int32_t* shapes, const double* maps_f64, const uint8_t* active, int nframes,
+                     double pixfrac, int kernel, int out_ny, int out_nx, void* out_rows);
+int spx_drizzle_f32(const void* rows, int nframes, int kernel, double fill, int out_ny, int out_nx, float* out_sci,
+                    float* out_wht, int32_t* out_ctx, void* stream);
+int spx_drizzle_f64(const void* rows, int nframes, int kernel, double fill, int out_ny, int out_nx, double* out_sci,
+                    float* out_wht, int32_t* out_ctx, void* stream);
 
 /*
  * Synthetic Gaussian-spot pairs: pair k = first_index + i has

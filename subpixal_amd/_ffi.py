@@ -13,6 +13,8 @@ LIB_PATH = os.environ.get('SPX_HIP_LIB') or os.path.join(_HERE, 'csrc', 'libsubp
 ABI_VERSION = 4
 MEASURE_COLUMNS = 13                                     # SPX_MEASURE_COLUMNS
 ERROR_COLUMNS = 6                                        # SPX_ERROR_COLUMNS
+DRIZZLE_ROW_BYTES = 224                                  # SPX_DRIZZLE_ROW_BYTES
+E_ARG, E_SHAPE = -1, -2                                  # SPX_E_ARG, SPX_E_SHAPE
 REFINE_DEFAULT, REFINE_F64, REFINE_F32 = 0, 1, 2         # SPX_REFINE_* (include/subpixal_hip.h)
 MAX_SIDE = 682
 MAX_UPSAMPLE = 59
@@ -86,6 +88,13 @@ _SIGNATURES = {
                                           _c.c_int, _c.c_int, _vp, _vp, _vp, _vp, _vp]),
     'spx_measure_errors_f64': (_c.c_int, [_vp, _vp, _c.c_double, _vp, _c.c_double, _vp, _c.c_double, _vp, _c.c_int,
                                           _c.c_int, _c.c_int, _vp, _vp, _vp, _vp, _vp]),
+    # drizzle: spx_drizzle_rows packs HOST tables (frames, weights, masks, shapes, maps, active, nframes, pixfrac,
+    # kernel, out_ny, out_nx, out_rows); spx_drizzle_*: device rows, nframes, kernel, fill, out_ny, out_nx, sci, wht,
+    # ctx, stream
+    'spx_drizzle_rows': (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _c.c_int, _c.c_double, _c.c_int, _c.c_int, _c.c_int,
+                                    _vp]),
+    'spx_drizzle_f32': (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_double, _c.c_int, _c.c_int, _vp, _vp, _vp, _vp]),
+    'spx_drizzle_f64': (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_double, _c.c_int, _c.c_int, _vp, _vp, _vp, _vp]),
     # deblending of merged sources (spx_deblend_labels_*): frame, mask, filter, fky, fkx, fny, fnx, labels,
     # nlabels, boxes, connectivity, min_area, nlevels, contrast, mode, work, work_bytes, out_labels, out_parent,
     # out_dflags, max_out, out_nlabels, stream

@@ -7,6 +7,9 @@ blots, ``cc.find_displacement`` -- for ALL sources in one kernel launch per cuto
 shape (the iterations are independent; nothing computed for source k feeds k+1 until
 the linear fit at align.py:720).
 
+``align_frames`` restates the loop around it (``align_images``, align.py:225-447) for affine maps: drizzle, find
+sources, re-drizzle without one frame, cut, blot, cross-correlate, fit, correct the frame's map.
+
 Not reproduced here (out of scope): the blotting itself
 (``blot.blot_cutout`` -> drizzlepac's C ``tblot``) and astropy WCS objects.  The caller
 supplies the dithered blots, either ready-made or through a ``blot`` callable with the
@@ -23,7 +26,7 @@ import numpy as np
 from . import _ffi, cc
 
 __all__ = ['find_linear_fit', 'iter_linear_fit', 'measure_shifts', 'measure_shifts_affine',
-           'usable_status', 'ST_SKIPPED']
+           'usable_status', 'ST_SKIPPED', 'align_frames', 'compose_fit']
 
 # per-source status of the measurement: the library's SPX_ST_* codes (include/subpixal_hip.h) or
 ST_SKIPPED = -1          # cutout shape outside what the kernels take (3.._ffi.MAX_SIDE = 682 px per side): not measured
@@ -420,3 +423,138 @@ def find_linear_fit(img_cutouts, drz_cutouts, wcslin=None, fitgeom='general',
     # meaningless shift.  The reference has no such guard: it would fit whatever came back.
     fit = _fit_from_shifts(img_dxy, status, xyim, xyref, weights, wcslin, fitgeom, nclip, sigma)
     return fit, interlaced_cc, nonshifted_blts
+
+
+# ----------------------------------------------------------------------------
+# the loop of align.py:225-447 for affine maps
+# ----------------------------------------------------------------------------
+def compose_fit(affine, fit):
+    """The corrected forward map ``M o G0`` of a frame whose map was ``affine`` (``[6]``, input pixel -> output
+    pixel) and whose ``find_linear_fit`` result is ``fit``.
+
+    Without WCS objects ``find_linear_fit`` fits G from 1-based image positions to where the blot puts the same
+    content (``xyim -> xyim + dxy``), and the blot is the model ``M^-1(output)``: the content at image position p
+    belongs at output position ``M(G0(p))`` with ``G0(p) = G(p + 1) - 1`` in 0-based pixels."""
+    m = np.asarray(affine, dtype=np.float64)
+    a, t = np.array([[m[0], m[1]], [m[3], m[4]]]), np.array([m[2], m[5]])
+    f = np.asarray(fit['fit_matrix'], dtype=np.float64)
+    c = np.asarray(fit.get('center', np.zeros(2)), dtype=np.float64)
+    g = f @ (np.ones(2) - c) + c + np.asarray(fit['offset'], dtype=np.float64) - 1.0
+    a2, t2 = a @ f, a @ g + t
+    return np.array([a2[0, 0], a2[0, 1], t2[0], a2[1, 0], a2[1, 1], t2[1]])
+
+
+def _frame_catalogs(q, name, prim, margin, dtype):
+    """The image and drizzled ``CutoutCatalog`` of frame ``name`` for the primary cutouts ``prim`` (a
+    ``CutoutCatalog`` of the full drizzle: boxes, ids, positions, weights, segmentation) against the leave-one-out
+    drizzle ``q``, and the per-source image-cutout -> drizzled-cutout affines.  Sources whose image box leaves the
+    frame, whose drizzled box leaves the output, or whose boxes leave the 3 .. 682 px range are dropped from both."""
+    from .cutout import CutoutCatalog
+    m = q.map(name)
+    a, t = np.array([[m[0], m[1]], [m[3], m[4]]]), np.array([m[2], m[5]])
+    ainv = np.linalg.inv(a)
+    frame = q._resident(name).data
+    fny, fnx = frame.shape
+    NY, NX = q.reference_image
+    b = prim.boxes.astype(np.float64)
+    # the four corners of the primary boxes (pixel centres) through M^-1; the bounding box, outwards
+    cx = np.stack([b[:, 0], b[:, 0] + b[:, 2] - 1, b[:, 0], b[:, 0] + b[:, 2] - 1], axis=1)
+    cy = np.stack([b[:, 1], b[:, 1], b[:, 1] + b[:, 3] - 1, b[:, 1] + b[:, 3] - 1], axis=1)
+    ix = ainv[0, 0] * (cx - t[0]) + ainv[0, 1] * (cy - t[1])
+    iy = ainv[1, 0] * (cx - t[0]) + ainv[1, 1] * (cy - t[1])
+    x0, x1 = np.floor(ix.min(axis=1)).astype(np.int64), np.ceil(ix.max(axis=1)).astype(np.int64)
+    y0, y1 = np.floor(iy.min(axis=1)).astype(np.int64), np.ceil(iy.max(axis=1)).astype(np.int64)
+    iboxes = np.stack([x0, y0, x1 - x0 + 1, y1 - y0 + 1], axis=1)
+    dboxes = prim.boxes.astype(np.int64) + np.array([-margin, -margin, 2 * margin, 2 * margin])
+    keep = (x0 >= 0) & (y0 >= 0) & (x1 < fnx) & (y1 < fny)
+    keep &= (dboxes[:, 0] >= 0) & (dboxes[:, 1] >= 0) & (dboxes[:, 0] + dboxes[:, 2] <= NX) & \
+            (dboxes[:, 1] + dboxes[:, 3] <= NY)
+    for bx in (iboxes, dboxes):
+        keep &= (bx[:, 2:].min(axis=1) >= 3) & (bx[:, 2:].max(axis=1) <= _ffi.MAX_SIDE)
+    iboxes, dboxes = iboxes[keep].astype(np.int32), dboxes[keep].astype(np.int32)
+    pos = prim.src_pos[keep]
+    ipos = (pos - t) @ ainv.T
+    wt = None if prim.src_weight is None else prim.src_weight[keep]
+    img_cat = CutoutCatalog(frame, iboxes, src_pos=ipos, src_id=prim.src_id[keep], dtype=dtype)
+    drz_cat = CutoutCatalog(q.output_sci, dboxes, src_pos=pos, src_weight=wt, src_id=prim.src_id[keep],
+                            mask=(q.output_wht == 0), segmentation_image=prim.segmentation_image, dtype=dtype)
+    # image-cutout pixel (u, v) -> frame (u + x0, v + y0) -> output through M -> drizzled-cutout pixel
+    n = len(iboxes)
+    aff = np.empty((n, 6))
+    aff[:, 0], aff[:, 1], aff[:, 3], aff[:, 4] = m[0], m[1], m[3], m[4]
+    aff[:, 2] = m[0] * iboxes[:, 0] + m[1] * iboxes[:, 1] + m[2] - dboxes[:, 0]
+    aff[:, 5] = m[3] * iboxes[:, 0] + m[4] * iboxes[:, 1] + m[5] - dboxes[:, 1]
+    return img_cat, drz_cat, aff
+
+
+def align_frames(resample, catalog, nmax_iter=3, fitgeom='general', nclip=3, sigma=3.0, use_weights=True,
+                 cc_type='NCC', pad=1, margin=None, history=False, min_shift=3e-3, timings=None):
+    """The reference's ``align_images`` loop (align.py:225-447) for affine maps, without WCS objects or files.
+
+    resample : :class:`subpixal_amd.resample.DeviceDrizzle`; its maps are corrected in place.
+    catalog : :class:`subpixal_amd.catalogs.DeviceImageCatalog` (detection parameters, mask and filters set).
+
+    Per iteration: ``resample.execute()``; the sources and the segmentation of ``output_sci``; then for every
+    frame k in list order, a copy of the drizzle re-made WITHOUT frame k (the previous frame, already corrected,
+    goes back in: ``fast_replace_image``), the drizzled cutouts from it with ``output_wht == 0`` as their mask
+    (align.py:308-313), the image cutouts of frame k in the primary boxes mapped through ``M_k^-1``,
+    ``find_linear_fit`` on the two, and ``set_map(k, M_k o G0)`` (:func:`compose_fit`) right away, as the
+    reference updates the WCS before the next image is aligned.  Stops after ``nmax_iter`` iterations or when every
+    frame's ``|offset|`` is below ``min_shift`` (align.py's ``eps_shift``).
+
+    margin : how far the drizzled cutouts reach beyond the primary boxes (default 6 px: the blot's quintic
+    needs 3, the rest is room for the map error).  timings : a dict that receives lists of host-synchronised
+    seconds per stage (``tools/bench_drizzle.py``), or None.
+
+    Returns the list, per iteration, of ``{name: fit}``; with ``history`` each fit also carries ``'map_before'``,
+    ``'map_after'`` and ``'nsources'``.  Polynomial distortion, cosmic-ray rejection, sky subtraction and FITS /
+    WCS write-back are out of scope."""
+    import time
+    import torch
+    margin = 6 if margin is None else int(margin)
+    if margin < 0 or nmax_iter < 1:
+        raise ValueError("align_frames: margin >= 0 and nmax_iter >= 1.")
+    dtype = resample.dtype
+
+    def lap(key, t0):
+        if timings is not None:
+            torch.cuda.synchronize()
+            timings.setdefault(key, []).append(time.perf_counter() - t0)
+        return time.perf_counter()
+
+    out = []
+    for _ in range(int(nmax_iter)):
+        t0 = time.perf_counter()
+        resample.execute()
+        t0 = lap('drizzle', t0)
+        catalog.set_image(resample.output_sci)
+        catalog.execute()
+        prim = catalog.cutout_catalog(resample.output_sci, pad=pad, dtype=dtype,
+                                      weight='pos_std' if use_weights else None)
+        t0 = lap('find_sources', t0)
+        if len(prim) == 0:
+            raise ValueError("align_frames: no sources in the drizzled image.")
+        q = resample.copy()
+        fits, previous, shifts = {}, None, []
+        for name in list(resample.input_image_names):
+            t0 = time.perf_counter()
+            q.fast_replace_image(name, previous)
+            previous = name
+            t0 = lap('leave_one_out', t0)
+            img_cat, drz_cat, aff = _frame_catalogs(q, name, prim, margin, dtype)
+            t0 = lap('catalogs', t0)
+            fit, _, _ = find_linear_fit(img_cat, drz_cat, affine=aff, fitgeom=fitgeom, nclip=nclip, sigma=sigma,
+                                        use_weights=use_weights, cc_type=cc_type)
+            t0 = lap('find_linear_fit', t0)
+            before = q.map(name)
+            after = compose_fit(before, fit)
+            resample.set_map(name, after)
+            q.set_map(name, after)
+            if history:
+                fit['map_before'], fit['map_after'], fit['nsources'] = before, after, len(img_cat)
+            fits[name] = fit
+            shifts.append(float(np.linalg.norm(fit['offset'])))
+        out.append(fits)
+        if max(shifts) < min_shift:
+            break
+    return out

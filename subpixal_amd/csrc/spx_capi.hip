@@ -10,12 +10,14 @@
 #include "spx_aux_kernels.h"
 #include "spx_detect_kernels.h"
 #include "spx_error_kernels.h"
+#include "spx_drizzle_kernels.h"
 #include "spx_deblend_kernels.h"
 #include "spx_background_kernels.h"
 #include "spx_tables.h"
 #include "../../include/subpixal_hip.h"
 
 #include <cstdlib>
+#include <cstring>
 #include <map>
 #include <mutex>
 #include <set>
@@ -1176,10 +1178,68 @@ int measure_errors(const T* frame, const uint8_t* bad, double bkg_scalar, const 
     SPX_HIP(hipGetLastError());
     return 0;
 }
+
+static_assert(sizeof(spx::DrizzleRow) == SPX_DRIZZLE_ROW_BYTES, "include/subpixal_hip.h states the row size");
+int drizzle_sizes(int nframes, int kernel, int out_ny, int out_nx) {
+    if (nframes < 1 || nframes > spx::kDrzMaxFrames) return fail(SPX_E_ARG, "nframes must be 1..128");
+    if (kernel < 0 || kernel > 2) return fail(SPX_E_ARG, "kernel must be 0 (square), 1 (turbo) or 2 (point)");
+    if (out_ny < 1 || out_nx < 1 || (int64_t)out_ny * out_nx >= 2147483647LL)
+        return fail(SPX_E_SHAPE, "the output must hold 1 .. 2^31 - 2 pixels");
+    return 0;
+}
+
+template <typename T>
+int drizzle(const void* rows, int nframes, int kernel, double fill, int out_ny, int out_nx, T* sci, float* wht,
+            int32_t* ctx, void* stream) {
+    if (const int rc = drizzle_sizes(nframes, kernel, out_ny, out_nx)) return rc;
+    if (!rows || !sci || !wht || !ctx) return fail(SPX_E_ARG, "null pointer");
+    const int64_t tiles = (int64_t)((out_nx + spx::kDrzTileW - 1) / spx::kDrzTileW) *
+                          ((out_ny + spx::kDrzTileH - 1) / spx::kDrzTileH);
+    hipLaunchKernelGGL(spx::drizzle_kernel<T>, dim3(capped_grid(tiles, 1 << 20)), dim3(256), 0,
+                       reinterpret_cast<hipStream_t>(stream), static_cast<const spx::DrizzleRow*>(rows), nframes,
+                       kernel, fill, out_ny, out_nx, sci, wht, ctx);
+    SPX_HIP(hipGetLastError());
+    return 0;
+}
 }  // namespace
 
 extern "C" {
 
+int spx_drizzle_rows(const void* const* frames, const void* const* weights, const uint8_t* const* masks,
+                     const int32_t* shapes, const double* maps_f64, const uint8_t* active, int nframes,
+                     double pixfrac, int kernel, int out_ny, int out_nx, void* out_rows) {
+    if (const int rc = drizzle_sizes(nframes, kernel, out_ny, out_nx)) return rc;
+    if (!(pixfrac > 0.0 && pixfrac <= 1.0)) return fail(SPX_E_ARG, "pixfrac must lie in (0, 1]");
+    if (!frames || !shapes || !maps_f64 || !out_rows) return fail(SPX_E_ARG, "null pointer");
+    for (int k = 0; k < nframes; ++k) {
+        if (!frames[k]) return fail(SPX_E_ARG, "null pointer: frame " + std::to_string(k));
+        const int ny = shapes[2 * k], nx = shapes[2 * k + 1];
+        if (ny < 1 || nx < 1 || (int64_t)ny * nx >= 2147483647LL)
+            return fail(SPX_E_SHAPE, "frame " + std::to_string(k) + " must hold 1 .. 2^31 - 2 pixels");
+    }
+    std::vector<spx::DrizzleRow> rows((size_t)nframes);
+    for (int k = 0; k < nframes; ++k) {
+        const int rc = spx::host::drizzle_pack_row(frames[k], weights ? weights[k] : nullptr,
+                                                   masks ? masks[k] : nullptr, shapes[2 * k], shapes[2 * k + 1],
+                                                   active ? active[k] : 1, maps_f64 + 6 * k, pixfrac, kernel,
+                                                   &rows[(size_t)k]);
+        if (rc == 1) return fail(SPX_E_ARG, "the map of frame " + std::to_string(k) + " has an entry that is not finite");
+        if (rc == 2) return fail(SPX_E_ARG, "the map of frame " + std::to_string(k) + " is singular");
+        if (rc == 3)
+            return fail(SPX_E_SHAPE, "the map of frame " + std::to_string(k) +
+                                         " shrinks the frame so far that one output pixel gathers from more than 8 x 8");
+    }
+    memcpy(out_rows, rows.data(), rows.size() * sizeof(spx::DrizzleRow));      // nothing is written on an error
+    return 0;
+}
+int spx_drizzle_f32(const void* rows, int nframes, int kernel, double fill, int out_ny, int out_nx, float* out_sci,
+                    float* out_wht, int32_t* out_ctx, void* stream) {
+    return drizzle<float>(rows, nframes, kernel, fill, out_ny, out_nx, out_sci, out_wht, out_ctx, stream);
+}
+int spx_drizzle_f64(const void* rows, int nframes, int kernel, double fill, int out_ny, int out_nx, double* out_sci,
+                    float* out_wht, int32_t* out_ctx, void* stream) {
+    return drizzle<double>(rows, nframes, kernel, fill, out_ny, out_nx, out_sci, out_wht, out_ctx, stream);
+}
 int spx_measure_errors_f32(const float* frame, const uint8_t* bad_mask, double bkg_scalar, const float* bkg_map,
                            double rms_scalar, const float* rms_map, double gain, const int32_t* labels, int fny,
                            int fnx, int nlabels, const int32_t* boxes, const double* table_f64,

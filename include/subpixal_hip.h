@@ -35,6 +35,9 @@
  *   spx_drizzle_rows, spx_drizzle_f32 / _f64
  *                               <-  Resample.execute / fast_replace_image (resample.py:535-625): the drizzle of
  *                                   the dithered frames, for affine maps; parity with drizzlepac UNPINNED.
+ *   spx_drizzle_median_f32 / _f64, spx_drizzle_cr_f32 / _f64
+ *                               <-  the cosmic-ray rejection of the same execute() (resample.py:366-390): median,
+ *                                   blot back, derivative, drizCR; parity with drizzlepac UNPINNED.
  *   spx_blot_affine4_f32        <-  the four blot_cutout(dzct, imct) calls per source of
  *                                   subpixal/align.py:664-676 (blot.py:79-155, drizzlepac
  *                                   tblot, interp='poly5') for coordinate maps that are
@@ -683,6 +686,76 @@ int spx_drizzle_f32(const void* rows, int nframes, int kernel, double fill, int 
                     float* out_wht, int32_t* out_ctx, void* stream);
 int spx_drizzle_f64(const void* rows, int nframes, int kernel, double fill, int out_ny, int out_nx, double* out_sci,
                     float* out_wht, int32_t* out_ctx, void* stream);
+
+/*
+ * Cosmic-ray rejection for the drizzle: the steps the reference's Resample.execute runs between its two drizzles
+ * (resample.py:366-390: median, blot back, derivative, drizCR).  drizzlepac is not in the reference tree, so, as for
+ * the drizzle itself, parity with it is UNPINNED: the definition is this library's own, modelled on drizzlepac's
+ * createMedian / ablot / quickDeriv / drizCR; tests/crreject_statement.py restates steps 2 .. 6 in numpy and the
+ * kernels are pinned against that (step 1 is the drizzle's own arithmetic, pinned by tests/drizzle_statement.py).
+ *
+ * DEFINITION -- notation of the drizzle above: frames k with rows, maps M_k, effective weights, pixfrac, a kernel.
+ *   1. Single-frame values.  For output pixel P and active frame k, num_k and wht_k are the drizzle's sums
+ *      restricted to frame k, in the same order, float64, contraction off.  s_k = (float)(num_k / wht_k), valid iff
+ *      wht_k > 0.  For float32 frames this is bit for bit what spx_drizzle_f32 writes with only frame k active.
+ *   2. Median.  m = the number of valid frames at P; nmed = m (uint8).  The m values are sorted ascending; if
+ *      m - nlow - nhigh >= 1 the nlow lowest and the nhigh highest are dropped, otherwise none.  med is the middle
+ *      value, for an even count (float)(0.5 * ((double)a + (double)b)) of the two middle values; med = 0 where
+ *      m = 0.  med is float32 for both frame dtypes.
+ *   3. Blot.  For input pixel (i, j) of frame k, (X, Y) = M_k(i, j) = ((a0 i + a1 j) + a2, (a3 i + a4 j) + a5) and
+ *      b(i, j) = the quintic of spx_blot_affine4_f32 (with its edge continuation) of med at (X, Y), float32.  With
+ *      ix = floor(X), iy = floor(Y), b is DEFINED iff 0 <= X <= NX-1 and 0 <= Y <= NY-1 and every med pixel of the
+ *      footprint [ix-2, ix+3] x [iy-2, iy+3], clipped to the grid, has nmed > 0.  b is also evaluated at positions
+ *      (i, j) outside the frame: the map is defined there.
+ *   4. Derivative.  D(i, j) = the largest |b(i, j) - b(n)| over those of the four neighbours n = (i+-1, j),
+ *      (i, j+-1) whose b is defined; 0 if none is.  float32.
+ *   5. Test.  A pixel is TESTABLE iff it lies inside the frame, its value is finite, it is not masked, its weight
+ *      (where a weight map is given) is finite and > 0, b is defined there, and its rms is finite and >= 0.  In
+ *      float64 with contraction off: t = |d - b|, var = rms^2 + (max(b - sky, 0) / gain if gain is finite and > 0,
+ *      else 0), fail_p = testable and t > scale_p * D + snr_p * sqrt(var), p = 1, 2.  rms is a per-frame scalar or a
+ *      map in the frame's dtype.  Pixels that are not testable never fail.
+ *   6. Mask.  crmask(i, j) = fail_2(i, j) and (some pixel of the 3 x 3 block around (i, j) has fail_1).
+ *      clean(i, j) = b cast to the frame dtype where crmask is 1; elsewhere d, unchanged, NaNs included.
+ *   drizzlepac's defaults: snr = (3.5, 3.0), scale = (1.2, 0.7), nlow = nhigh = 0, sky = 0, no gain.
+ *   Not here: minmed and the other combine types, driz_cr_grow and the CTE tail, static masks, sky subtraction.
+ *
+ * Both entries take the DEVICE table spx_drizzle_rows packed and only launch, as spx_drizzle_* do; neither has an
+ * atomic or depends on the grid, so every output is the same bit pattern on every run.  They can be captured, with
+ * one exception: the first spx_drizzle_median_* call on a device with nactive > 64 (more than 64 KiB of LDS) raises the
+ * kernel's dynamic-LDS limit before it launches, so make that call once outside a capture; later calls only launch.
+ *
+ * spx_drizzle_median_f32 / _f64 -- steps 1 and 2 over the rows' own masks
+ *   nactive  : the number of rows whose `active` flag is set (the caller counts them when it packs the rows); the
+ *              launch takes nactive * 1024 bytes of LDS per workgroup.  Values of active rows beyond that count
+ *              would be dropped.
+ *   kernel   : the kernel the rows were packed for;  nlow, nhigh >= 0
+ *   out_med  : float32 [out_ny][out_nx];  out_nmed : uint8 [out_ny][out_nx]
+ *   SPX_E_ARG: a null pointer, nframes outside 1 .. 128, nactive outside 1 .. nframes, unknown kernel, nlow or nhigh
+ *   < 0.  SPX_E_SHAPE: output size as for spx_drizzle_*.  Checked before any HIP call.
+ *
+ * spx_drizzle_cr_f32 / _f64 -- steps 3 .. 6 for row `frame` of the table (its data, weight, mask, shape and map)
+ *   fny, fnx : the frame's shape; they size the grid only, the kernel addresses by the row's own ny, nx
+ *   med, nmed: what spx_drizzle_median_* wrote for the (out_ny, out_nx) grid, at least 6 x 6 (the quintic's edge
+ *              continuation)
+ *   rms_scalar, rms_map : the frame's noise, a scalar, or (rms_map not NULL) a map of the frame's shape and dtype
+ *   sky, gain: of step 5; a gain that is not finite or not > 0 switches the Poisson term off; sky must be finite
+ *   out_crmask : uint8 [ny][nx];  out_clean : [ny][nx] in the frame dtype; it must not be the frame itself
+ *   SPX_E_ARG: a null pointer (rms_map may be NULL), nframes outside 1 .. 128, frame outside 0 .. nframes-1, an snr
+ *   or scale that is not finite or < 0, snr2 > snr1, scale2 > scale1, a sky that is not finite.  SPX_E_SHAPE: a
+ *   frame or output with a side < 1 or 2^31 - 1 pixels or more, an output below 6 x 6.  Checked before any HIP call.
+ */
+int spx_drizzle_median_f32(const void* rows, int nframes, int nactive, int kernel, int nlow, int nhigh, int out_ny,
+                           int out_nx, float* out_med, uint8_t* out_nmed, void* stream);
+int spx_drizzle_median_f64(const void* rows, int nframes, int nactive, int kernel, int nlow, int nhigh, int out_ny,
+                           int out_nx, float* out_med, uint8_t* out_nmed, void* stream);
+int spx_drizzle_cr_f32(const void* rows, int nframes, int frame, int fny, int fnx, const float* med,
+                       const uint8_t* nmed, int out_ny, int out_nx, double rms_scalar, const float* rms_map, double sky,
+                       double gain, double snr1, double snr2, double scale1, double scale2, uint8_t* out_crmask,
+                       float* out_clean, void* stream);
+int spx_drizzle_cr_f64(const void* rows, int nframes, int frame, int fny, int fnx, const float* med,
+                       const uint8_t* nmed, int out_ny, int out_nx, double rms_scalar, const double* rms_map,
+                       double sky, double gain, double snr1, double snr2, double scale1, double scale2,
+                       uint8_t* out_crmask, double* out_clean, void* stream);
 
 /*
  * Synthetic Gaussian-spot pairs: pair k = first_index + i has

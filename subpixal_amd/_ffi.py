@@ -95,6 +95,19 @@ _SIGNATURES = {
                                     _vp]),
     'spx_drizzle_f32': (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_double, _c.c_int, _c.c_int, _vp, _vp, _vp, _vp]),
     'spx_drizzle_f64': (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_double, _c.c_int, _c.c_int, _vp, _vp, _vp, _vp]),
+    # cosmic-ray rejection.  spx_drizzle_median_*: device rows, nframes, nactive, kernel, nlow, nhigh, out_ny, out_nx,
+    # med, nmed, stream; spx_drizzle_cr_*: device rows, nframes, frame, fny, fnx, med, nmed, out_ny, out_nx, rms,
+    # rms_map, sky, gain, snr1, snr2, scale1, scale2, crmask, clean, stream
+    'spx_drizzle_median_f32': (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
+                                          _vp, _vp, _vp]),
+    'spx_drizzle_median_f64': (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
+                                          _vp, _vp, _vp]),
+    'spx_drizzle_cr_f32': (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _vp, _vp, _c.c_int, _c.c_int,
+                                      _c.c_double, _vp, _c.c_double, _c.c_double, _c.c_double, _c.c_double,
+                                      _c.c_double, _c.c_double, _vp, _vp, _vp]),
+    'spx_drizzle_cr_f64': (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _vp, _vp, _c.c_int, _c.c_int,
+                                      _c.c_double, _vp, _c.c_double, _c.c_double, _c.c_double, _c.c_double,
+                                      _c.c_double, _c.c_double, _vp, _vp, _vp]),
     # deblending of merged sources (spx_deblend_labels_*): frame, mask, filter, fky, fkx, fny, fnx, labels,
     # nlabels, boxes, connectivity, min_area, nlevels, contrast, mode, work, work_bytes, out_labels, out_parent,
     # out_dflags, max_out, out_nlabels, stream

@@ -448,12 +448,17 @@ def _frame_catalogs(q, name, prim, margin, dtype):
     """The image and drizzled ``CutoutCatalog`` of frame ``name`` for the primary cutouts ``prim`` (a
     ``CutoutCatalog`` of the full drizzle: boxes, ids, positions, weights, segmentation) against the leave-one-out
     drizzle ``q``, and the per-source image-cutout -> drizzled-cutout affines.  Sources whose image box leaves the
-    frame, whose drizzled box leaves the output, or whose boxes leave the 3 .. 682 px range are dropped from both."""
+    frame, whose drizzled box leaves the output, or whose boxes leave the 3 .. 682 px range are dropped from both.
+    The image cutouts are cut from ``q.crclean(name)`` -- the frame with its rejected cosmic rays replaced by the
+    blotted median -- where the drizzle has one (``cr_reject=True``), else from the frame itself, as the
+    reference's ``imfile if crclean_image is None else crclean_image`` (align.py:291-330)."""
     from .cutout import CutoutCatalog
     m = q.map(name)
     a, t = np.array([[m[0], m[1]], [m[3], m[4]]]), np.array([m[2], m[5]])
     ainv = np.linalg.inv(a)
     frame = q._resident(name).data
+    if q.crclean(name) is not None:                 # align.py:330: the CR-cleaned frame where there is one
+        frame = q.crclean(name)
     fny, fnx = frame.shape
     NY, NX = q.reference_image
     b = prim.boxes.astype(np.float64)
@@ -507,8 +512,10 @@ def align_frames(resample, catalog, nmax_iter=3, fitgeom='general', nclip=3, sig
     seconds per stage (``tools/bench_drizzle.py``), or None.
 
     Returns the list, per iteration, of ``{name: fit}``; with ``history`` each fit also carries ``'map_before'``,
-    ``'map_after'`` and ``'nsources'``.  Polynomial distortion, cosmic-ray rejection, sky subtraction and FITS /
-    WCS write-back are out of scope."""
+    ``'map_after'`` and ``'nsources'``.  Polynomial distortion, sky subtraction and FITS /
+    WCS write-back are out of scope.  Cosmic rays are rejected when ``resample`` was built with ``cr_reject=True``:
+    the full ``execute()`` of every iteration makes the masks and the cleaned frames, the leave-one-out drizzles
+    reuse the masks and the image cutouts come from the cleaned frames."""
     import time
     import torch
     margin = 6 if margin is None else int(margin)

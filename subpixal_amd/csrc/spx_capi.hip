@@ -11,6 +11,7 @@
 #include "spx_detect_kernels.h"
 #include "spx_error_kernels.h"
 #include "spx_drizzle_kernels.h"
+#include "spx_crreject_kernels.h"
 #include "spx_deblend_kernels.h"
 #include "spx_background_kernels.h"
 #include "spx_tables.h"
@@ -1201,6 +1202,70 @@ int drizzle(const void* rows, int nframes, int kernel, double fill, int out_ny, 
     SPX_HIP(hipGetLastError());
     return 0;
 }
+
+// cosmic-ray rejection (spx_crreject_kernels.h)
+std::mutex g_crr_mu;
+std::set<std::pair<int, const void*>> g_crr_lds_ok;       // (device, kernel) whose dynamic-LDS limit is raised
+
+template <typename T>
+int drizzle_median(const void* rows, int nframes, int nactive, int kernel, int nlow, int nhigh, int out_ny, int out_nx,
+                   float* med, uint8_t* nmed, void* stream) {
+    if (const int rc = drizzle_sizes(nframes, kernel, out_ny, out_nx)) return rc;
+    if (nactive < 1 || nactive > nframes) return fail(SPX_E_ARG, "nactive must be 1..nframes");
+    if (nlow < 0 || nhigh < 0) return fail(SPX_E_ARG, "nlow and nhigh must not be negative");
+    if (!rows || !med || !nmed) return fail(SPX_E_ARG, "null pointer");
+    // no pixel has more than 128 values: larger counts mean the same and cannot overflow m - nlow - nhigh
+    if (nlow > spx::kDrzMaxFrames) nlow = spx::kDrzMaxFrames;
+    if (nhigh > spx::kDrzMaxFrames) nhigh = spx::kDrzMaxFrames;
+    const int lds = (int)spx::drizzle_median_lds_bytes(nactive);
+    auto kern = spx::drizzle_median_kernel<T>;
+    if (lds > 64 * 1024) {
+        int dev = 0;
+        SPX_HIP(hipGetDevice(&dev));
+        std::lock_guard<std::mutex> lk(g_crr_mu);
+        const auto key = std::make_pair(dev, reinterpret_cast<const void*>(kern));
+        if (!g_crr_lds_ok.count(key)) {
+            SPX_HIP(hipFuncSetAttribute(key.second, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        (int)spx::drizzle_median_lds_bytes(spx::kDrzMaxFrames)));
+            g_crr_lds_ok.insert(key);
+        }
+    }
+    const int64_t tiles = (int64_t)((out_nx + spx::kDrzTileW - 1) / spx::kDrzTileW) *
+                          ((out_ny + spx::kDrzTileH - 1) / spx::kDrzTileH);
+    hipLaunchKernelGGL(kern, dim3(capped_grid(tiles, 1 << 20)), dim3(256), lds, reinterpret_cast<hipStream_t>(stream),
+                       static_cast<const spx::DrizzleRow*>(rows), nframes, nactive, kernel, nlow, nhigh, out_ny, out_nx,
+                       med, nmed);
+    SPX_HIP(hipGetLastError());
+    return 0;
+}
+
+bool cr_level_ok(double v) { return v - v == 0.0 && v >= 0.0; }
+
+template <typename T>
+int drizzle_cr(const void* rows, int nframes, int frame, int fny, int fnx, const float* med, const uint8_t* nmed,
+               int out_ny, int out_nx, double rms_scalar, const T* rms_map, double sky, double gain, double snr1,
+               double snr2, double scale1, double scale2, uint8_t* crmask, T* clean, void* stream) {
+    if (const int rc = drizzle_sizes(nframes, 0, out_ny, out_nx)) return rc;
+    if (frame < 0 || frame >= nframes) return fail(SPX_E_ARG, "frame must be a row of the table, 0..nframes-1");
+    if (!cr_level_ok(snr1) || !cr_level_ok(snr2) || !cr_level_ok(scale1) || !cr_level_ok(scale2))
+        return fail(SPX_E_ARG, "snr and scale must be finite and not negative");
+    if (snr2 > snr1 || scale2 > scale1)
+        return fail(SPX_E_ARG, "the second test must not be the stricter one: snr2 <= snr1 and scale2 <= scale1");
+    if (!(sky - sky == 0.0)) return fail(SPX_E_ARG, "sky must be finite");
+    if (!rows || !med || !nmed || !crmask || !clean) return fail(SPX_E_ARG, "null pointer");
+    if (fny < 1 || fnx < 1 || (int64_t)fny * fnx >= 2147483647LL)
+        return fail(SPX_E_SHAPE, "the frame must hold 1 .. 2^31 - 2 pixels");
+    if (out_ny < spx::kCrMinOut || out_nx < spx::kCrMinOut)
+        return fail(SPX_E_SHAPE, "the blot's quintic needs a median of 6 x 6 pixels at least");
+    const spx::CrParams c = spx::host::cr_params(rms_scalar, sky, gain, snr1, snr2, scale1, scale2);
+    const int64_t tiles = (int64_t)((fnx + spx::kDrzTileW - 1) / spx::kDrzTileW) *
+                          ((fny + spx::kDrzTileH - 1) / spx::kDrzTileH);
+    hipLaunchKernelGGL(spx::drizzle_cr_kernel<T>, dim3(capped_grid(tiles, 1 << 20)), dim3(256), spx::kCrLdsBytes,
+                       reinterpret_cast<hipStream_t>(stream), static_cast<const spx::DrizzleRow*>(rows), frame, med,
+                       nmed, out_ny, out_nx, rms_map, c, crmask, clean);
+    SPX_HIP(hipGetLastError());
+    return 0;
+}
 }  // namespace
 
 extern "C" {
@@ -1239,6 +1304,28 @@ int spx_drizzle_f32(const void* rows, int nframes, int kernel, double fill, int 
 int spx_drizzle_f64(const void* rows, int nframes, int kernel, double fill, int out_ny, int out_nx, double* out_sci,
                     float* out_wht, int32_t* out_ctx, void* stream) {
     return drizzle<double>(rows, nframes, kernel, fill, out_ny, out_nx, out_sci, out_wht, out_ctx, stream);
+}
+int spx_drizzle_median_f32(const void* rows, int nframes, int nactive, int kernel, int nlow, int nhigh, int out_ny,
+                           int out_nx, float* out_med, uint8_t* out_nmed, void* stream) {
+    return drizzle_median<float>(rows, nframes, nactive, kernel, nlow, nhigh, out_ny, out_nx, out_med, out_nmed, stream);
+}
+int spx_drizzle_median_f64(const void* rows, int nframes, int nactive, int kernel, int nlow, int nhigh, int out_ny,
+                           int out_nx, float* out_med, uint8_t* out_nmed, void* stream) {
+    return drizzle_median<double>(rows, nframes, nactive, kernel, nlow, nhigh, out_ny, out_nx, out_med, out_nmed, stream);
+}
+int spx_drizzle_cr_f32(const void* rows, int nframes, int frame, int fny, int fnx, const float* med,
+                       const uint8_t* nmed, int out_ny, int out_nx, double rms_scalar, const float* rms_map, double sky,
+                       double gain, double snr1, double snr2, double scale1, double scale2, uint8_t* out_crmask,
+                       float* out_clean, void* stream) {
+    return drizzle_cr<float>(rows, nframes, frame, fny, fnx, med, nmed, out_ny, out_nx, rms_scalar, rms_map, sky, gain,
+                             snr1, snr2, scale1, scale2, out_crmask, out_clean, stream);
+}
+int spx_drizzle_cr_f64(const void* rows, int nframes, int frame, int fny, int fnx, const float* med,
+                       const uint8_t* nmed, int out_ny, int out_nx, double rms_scalar, const double* rms_map,
+                       double sky, double gain, double snr1, double snr2, double scale1, double scale2,
+                       uint8_t* out_crmask, double* out_clean, void* stream) {
+    return drizzle_cr<double>(rows, nframes, frame, fny, fnx, med, nmed, out_ny, out_nx, rms_scalar, rms_map, sky, gain,
+                              snr1, snr2, scale1, scale2, out_crmask, out_clean, stream);
 }
 int spx_measure_errors_f32(const float* frame, const uint8_t* bad_mask, double bkg_scalar, const float* bkg_map,
                            double rms_scalar, const float* rms_map, double gain, const int32_t* labels, int fny,

@@ -171,6 +171,63 @@ SPX_DEVICE double drz_overlap(const DrizzleRow& r, int kernel, double cx, double
     return ar > kDrzDropArea ? ar * r.inv_norm : 0.0;
 }
 
+// The frame against a 32 x 8 output tile (centre (tcx, tcy), half-sides (thx, thy), in output pixels): the inverse
+// image of the tile's bounding box, grown by the window (and by one pixel against the rounding of the centre), is
+// compared with the frame as a whole.  True: no pixel of the frame reaches any pixel of the tile.
+SPX_DEVICE bool drz_frame_misses_tile(const DrizzleRow& r, double tcx, double tcy, double thx, double thy) {
+#pragma clang fp contract(off)
+    const double ux = tcx - r.a[2], uy = tcy - r.a[5];
+    const double ccx = r.inv[0] * ux + r.inv[1] * uy, ccy = r.inv[2] * ux + r.inv[3] * uy;
+    const double ex = fabs(r.inv[0]) * thx + fabs(r.inv[1]) * thy + r.rx + 1.0;
+    const double ey = fabs(r.inv[2]) * thx + fabs(r.inv[3]) * thy + r.ry + 1.0;
+    return ccx + ex < 0.0 || ccx - ex > (double)(r.nx - 1) || ccy + ey < 0.0 || ccy - ey > (double)(r.ny - 1);
+}
+
+// Adds frame r's terms for output pixel (X, Y) to num and den in the definition's order (j ascending, then i
+// ascending); true iff one of them had a w > 0.  drizzle_kernel carries num and den across the frames,
+// drizzle_median_kernel (spx_crreject_kernels.h) starts every frame from 0.
+template <typename T>
+SPX_DEVICE bool drz_frame_sums(const DrizzleRow& r, int kernel, int X, int Y, double& num, double& den) {
+#pragma clang fp contract(off)
+    const double ux = (double)X - r.a[2], uy = (double)Y - r.a[5];
+    const double px = r.inv[0] * ux + r.inv[1] * uy, py = r.inv[2] * ux + r.inv[3] * uy;
+    int i0 = (int)ceil(fmax(px - r.rx, -1.0)), i1 = (int)floor(fmin(px + r.rx, (double)r.nx));
+    int j0 = (int)ceil(fmax(py - r.ry, -1.0)), j1 = (int)floor(fmin(py + r.ry, (double)r.ny));
+    if (i0 < 0) i0 = 0;
+    if (j0 < 0) j0 = 0;
+    if (i1 > r.nx - 1) i1 = r.nx - 1;
+    if (j1 > r.ny - 1) j1 = r.ny - 1;
+    const T* __restrict__ D = static_cast<const T*>(r.data);
+    const T* __restrict__ W = static_cast<const T*>(r.weight);
+    const double lx = (double)X - 0.5, ly = (double)Y - 0.5;
+    bool hit = false;
+    for (int j = j0; j <= j1; ++j) {
+        for (int i = i0; i <= i1; ++i) {
+            // the drop's centre in the output, then in the pixel's own coordinates
+            const double CX = (r.a[0] * (double)i + r.a[1] * (double)j) + r.a[2];
+            const double CY = (r.a[3] * (double)i + r.a[4] * (double)j) + r.a[5];
+            const double a = kernel == kDrzPoint
+                                 ? (floor(CX + 0.5) == (double)X && floor(CY + 0.5) == (double)Y ? 1.0 : 0.0)
+                                 : drz_overlap(r, kernel, CX - lx, CY - ly);
+            if (!(a > 0.0)) continue;
+            const int64_t q = (int64_t)j * r.nx + i;
+            const T d = D[q];
+            if (!(d - d == T(0)) || (r.mask && r.mask[q])) continue;
+            double w = 1.0;
+            if (W) {
+                const T wv = W[q];
+                if (!(wv - wv == T(0)) || !(wv > T(0))) continue;
+                w = (double)wv;
+            }
+            const double aw = a * w;
+            num += aw * (double)d;
+            den += aw;
+            if (aw > 0.0) hit = true;
+        }
+    }
+    return hit;
+}
+
 template <typename T>
 SPX_TKERNEL(256)
 void drizzle_kernel(const DrizzleRow* __restrict__ rows, int nframes, int kernel, double fill, int out_ny, int out_nx,
@@ -196,54 +253,9 @@ void drizzle_kernel(const DrizzleRow* __restrict__ rows, int nframes, int kernel
             }
             const DrizzleRow& r = rows[k];
             if (!r.active) continue;
-            // the frame against the tile: the inverse image of the tile's bounding box, grown by the window
-            // (and by one pixel against the rounding of the centre), is compared with the frame as a whole
-            {
-                const double ux = tcx - r.a[2], uy = tcy - r.a[5];
-                const double ccx = r.inv[0] * ux + r.inv[1] * uy, ccy = r.inv[2] * ux + r.inv[3] * uy;
-                const double ex = fabs(r.inv[0]) * thx + fabs(r.inv[1]) * thy + r.rx + 1.0;
-                const double ey = fabs(r.inv[2]) * thx + fabs(r.inv[3]) * thy + r.ry + 1.0;
-                if (ccx + ex < 0.0 || ccx - ex > (double)(r.nx - 1) || ccy + ey < 0.0 || ccy - ey > (double)(r.ny - 1))
-                    continue;
-            }
+            if (drz_frame_misses_tile(r, tcx, tcy, thx, thy)) continue;
             if (!inside) continue;
-            const double ux = (double)X - r.a[2], uy = (double)Y - r.a[5];
-            const double px = r.inv[0] * ux + r.inv[1] * uy, py = r.inv[2] * ux + r.inv[3] * uy;
-            int i0 = (int)ceil(fmax(px - r.rx, -1.0)), i1 = (int)floor(fmin(px + r.rx, (double)r.nx));
-            int j0 = (int)ceil(fmax(py - r.ry, -1.0)), j1 = (int)floor(fmin(py + r.ry, (double)r.ny));
-            if (i0 < 0) i0 = 0;
-            if (j0 < 0) j0 = 0;
-            if (i1 > r.nx - 1) i1 = r.nx - 1;
-            if (j1 > r.ny - 1) j1 = r.ny - 1;
-            const T* __restrict__ D = static_cast<const T*>(r.data);
-            const T* __restrict__ W = static_cast<const T*>(r.weight);
-            const double lx = (double)X - 0.5, ly = (double)Y - 0.5;
-            bool hit = false;
-            for (int j = j0; j <= j1; ++j) {
-                for (int i = i0; i <= i1; ++i) {
-                    // the drop's centre in the output, then in the pixel's own coordinates
-                    const double CX = (r.a[0] * (double)i + r.a[1] * (double)j) + r.a[2];
-                    const double CY = (r.a[3] * (double)i + r.a[4] * (double)j) + r.a[5];
-                    const double a = kernel == kDrzPoint
-                                         ? (floor(CX + 0.5) == (double)X && floor(CY + 0.5) == (double)Y ? 1.0 : 0.0)
-                                         : drz_overlap(r, kernel, CX - lx, CY - ly);
-                    if (!(a > 0.0)) continue;
-                    const int64_t q = (int64_t)j * r.nx + i;
-                    const T d = D[q];
-                    if (!(d - d == T(0)) || (r.mask && r.mask[q])) continue;
-                    double w = 1.0;
-                    if (W) {
-                        const T wv = W[q];
-                        if (!(wv - wv == T(0)) || !(wv > T(0))) continue;
-                        w = (double)wv;
-                    }
-                    const double aw = a * w;
-                    num += aw * (double)d;
-                    den += aw;
-                    if (aw > 0.0) hit = true;
-                }
-            }
-            if (hit) word |= 1u << (k & 31);
+            if (drz_frame_sums<T>(r, kernel, X, Y, num, den)) word |= 1u << (k & 31);
         }
         if (inside) {
             ctx[(int64_t)((nframes - 1) >> 5) * plane + o] = (int32_t)word;

@@ -35,6 +35,8 @@
  *   spx_drizzle_rows, spx_drizzle_f32 / _f64
  *                               <-  Resample.execute / fast_replace_image (resample.py:535-625): the drizzle of
  *                                   the dithered frames, for affine maps; parity with drizzlepac UNPINNED.
+ *   spx_drizzle_poly_rows, spx_drizzle_poly_f32 / _f64
+ *                               <-  the same drizzle for frames with polynomial distortion maps (degree 1 .. 5).
  *   spx_drizzle_median_f32 / _f64, spx_drizzle_cr_f32 / _f64
  *                               <-  the cosmic-ray rejection of the same execute() (resample.py:366-390): median,
  *                                   blot back, derivative, drizCR; parity with drizzlepac UNPINNED.
@@ -686,6 +688,65 @@ int spx_drizzle_f32(const void* rows, int nframes, int kernel, double fill, int 
                     float* out_wht, int32_t* out_ctx, void* stream);
 int spx_drizzle_f64(const void* rows, int nframes, int kernel, double fill, int out_ny, int out_nx, double* out_sci,
                     float* out_wht, int32_t* out_ctx, void* stream);
+
+/*
+ * Drizzle for frames with polynomial distortion maps: spx_drizzle_poly_rows, spx_drizzle_poly_f32 / _f64.
+ *
+ * DEFINITION.  Everything of the drizzle above that is not named here is unchanged: pixel convention, effective
+ * weight, accumulation order (k, then j, then i ascending), float64 with contraction off, sci = num / wht, fill, ctx,
+ * the 1e-12 px^2 drop threshold, and no scale^2 applied.
+ *   Map of frame k: a bivariate polynomial of total degree `degree` (1 .. 5) in the input position relative to a
+ *   per-frame centre (xc, yc):  u = x - xc, v = y - yc,
+ *       X = sum_{d=0..degree} sum_{i=d..0} coef[0][k] u^i v^(d-i),   k = d (d + 1) / 2 + (d - i),
+ *       Y likewise with coef[1][k];
+ *   coef is float64 [2][21]: the term order and the 21 slots of spx_blot_poly4_f32; slots above `degree` are ignored.
+ *   Evaluation order.  spx_drizzle_poly_rows re-expands the map about the frame's own centre
+ *   (xf, yf) = ((nx - 1) / 2, (ny - 1) / 2) in extended precision and rounds each coefficient once, so the centre a
+ *   map is given about does not matter to the result.  A position is (u, v) = ((i - xf) +- p/2, (j - yf) +- p/2) and
+ *   the value a nested Horner scheme, powers of v outside and of u inside:
+ *       acc = c(0, D);  for j = D-1 .. 0 { r = c(D-j, j); for i = D-j-1 .. 0: r = r u + c(i, j);  acc = acc v + r }
+ *   (c(i, j) the coefficient of u^i v^j; D (D + 3) / 2 multiply-add pairs).  A computed coordinate is within
+ *   (4 D + 3) eps sum |c(i, j) u^i v^j| of the polynomial's value: 2 D roundings on the longest path through the
+ *   scheme, D ulps of the sum for the rounding of u and as many for v, 1 for the coefficients, 2 to spare.
+ *   kernel 0 'square': Q is the quadrilateral with straight edges whose vertices are M applied to the four corners
+ *                      (i -+ p/2, j -+ p/2) of the drop, in that cyclic order; a = area(Q n P_XY) / area(Q), both
+ *                      areas absolute values (a mirrored map comes out right).  For a degree-1 map this is the affine
+ *                      definition (area(Q) = |det A| p^2).
+ *   kernel 1 'turbo' : the axis-aligned square of side s = p sqrt|det J(i, j)| centred on M(i, j), J the analytic
+ *                      Jacobian of M at the pixel centre; a = overlap / (s s).
+ *   kernel 2 'point' : a = 1 on the pixel that holds M(i, j).
+ *
+ * spx_drizzle_poly_rows -- the sibling of spx_drizzle_rows: every array is a HOST array
+ *   frames, weights, masks, shapes, active, pixfrac, kernel, out_ny, out_nx: as for spx_drizzle_rows
+ *   coef_f64   : float64 [nframes][2][21]
+ *   degree     : int32 [nframes], 1 .. 5 (an affine frame is a degree-1 row)
+ *   center_f64 : float64 [nframes][2] = (xc, yc)
+ *   out_rows   : HOST buffer of nframes * SPX_DRIZZLE_POLY_ROW_BYTES.  A row's first 40 bytes are laid out as the
+ *                affine row's (data, weight and mask pointers, ny, nx, active, reserved); then the re-expanded
+ *                coefficients, the frame's centre, the inverse of the Jacobian at that centre and the number of chord
+ *                iterations (the kernel's inverse estimate), the candidate window (rx, ry), the reach of the linear
+ *                estimate (the tile skip) and the bounds of a drop's bounding half-sides over the whole frame, all
+ *                computed once in float64.  csrc/spx_drizzle_poly_kernels.h says why no drop with a non-zero overlap
+ *                can fall outside the window.
+ *   SPX_E_ARG: as spx_drizzle_rows, and: a degree outside 1 .. 5; a used coefficient or a centre that is not finite;
+ *   a map whose Jacobian determinant is zero, not finite or of both signs over the frame, checked on a lattice of
+ *   33 x 33 positions evenly spaced from -1/2 to nx - 1/2 and -1/2 to ny - 1/2 (the frame's border, corners and
+ *   centre among them).  SPX_E_SHAPE: as spx_drizzle_rows; a map under which some output pixel would gather from
+ *   more than 8 x 8 input pixels anywhere in the frame (2 rx + 1 > 8), or whose Jacobian varies by half or more of
+ *   itself over the frame (no window can be given).  On an error nothing is written.
+ *
+ * spx_drizzle_poly_f32 / _f64 -- take the DEVICE copy of those rows and only launch: capturable, no hidden copies.
+ *   Arguments, outputs and errors exactly as spx_drizzle_f32 / _f64, checked before any HIP call.
+ */
+#define SPX_DRIZZLE_POLY_ROW_BYTES 488
+int spx_drizzle_poly_rows(const void* const* frames, const void* const* weights, const uint8_t* const* masks,
+                          const int32_t* shapes, const double* coef_f64, const int32_t* degree,
+                          const double* center_f64, const uint8_t* active, int nframes, double pixfrac, int kernel,
+                          int out_ny, int out_nx, void* out_rows);
+int spx_drizzle_poly_f32(const void* rows, int nframes, int kernel, double fill, int out_ny, int out_nx, float* out_sci,
+                         float* out_wht, int32_t* out_ctx, void* stream);
+int spx_drizzle_poly_f64(const void* rows, int nframes, int kernel, double fill, int out_ny, int out_nx,
+                         double* out_sci, float* out_wht, int32_t* out_ctx, void* stream);
 
 /*
  * Cosmic-ray rejection for the drizzle: the steps the reference's Resample.execute runs between its two drizzles

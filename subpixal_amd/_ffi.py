@@ -14,6 +14,11 @@ ABI_VERSION = 4
 MEASURE_COLUMNS = 13                                     # SPX_MEASURE_COLUMNS
 ERROR_COLUMNS = 6                                        # SPX_ERROR_COLUMNS
 DRIZZLE_ROW_BYTES = 224                                  # SPX_DRIZZLE_ROW_BYTES
+DRIZZLE_POLY_ROW_BYTES = 488                             # SPX_DRIZZLE_POLY_ROW_BYTES
+# byte offsets of a packed polynomial row's fields (csrc/spx_drizzle_poly_kernels.h: DrizzlePolyRow): coef [2][21],
+# the frame's centre, A^-1, the window (rx, ry), the drop bounds (bx, by), degree and steps (two int32)
+DRIZZLE_POLY_ROW_COEF, DRIZZLE_POLY_ROW_CENTER, DRIZZLE_POLY_ROW_INV = 40, 376, 392
+DRIZZLE_POLY_ROW_WINDOW, DRIZZLE_POLY_ROW_DROP, DRIZZLE_POLY_ROW_DEGREE = 424, 456, 480
 E_ARG, E_SHAPE = -1, -2                                  # SPX_E_ARG, SPX_E_SHAPE
 REFINE_DEFAULT, REFINE_F64, REFINE_F32 = 0, 1, 2         # SPX_REFINE_* (include/subpixal_hip.h)
 MAX_SIDE = 682
@@ -95,6 +100,13 @@ _SIGNATURES = {
                                     _vp]),
     'spx_drizzle_f32': (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_double, _c.c_int, _c.c_int, _vp, _vp, _vp, _vp]),
     'spx_drizzle_f64': (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_double, _c.c_int, _c.c_int, _vp, _vp, _vp, _vp]),
+    # drizzle through polynomial maps: spx_drizzle_poly_rows packs HOST tables (frames, weights, masks, shapes, coef
+    # [K][2][21], degree [K], center [K][2], active, nframes, pixfrac, kernel, out_ny, out_nx, out_rows);
+    # spx_drizzle_poly_*: as spx_drizzle_*
+    'spx_drizzle_poly_rows': (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c.c_int, _c.c_double, _c.c_int,
+                                         _c.c_int, _c.c_int, _vp]),
+    'spx_drizzle_poly_f32': (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_double, _c.c_int, _c.c_int, _vp, _vp, _vp, _vp]),
+    'spx_drizzle_poly_f64': (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_double, _c.c_int, _c.c_int, _vp, _vp, _vp, _vp]),
     # cosmic-ray rejection.  spx_drizzle_median_*: device rows, nframes, nactive, kernel, nlow, nhigh, out_ny, out_nx,
     # med, nmed, stream; spx_drizzle_cr_*: device rows, nframes, frame, fny, fnx, med, nmed, out_ny, out_nx, rms,
     # rms_map, sky, gain, snr1, snr2, scale1, scale2, crmask, clean, stream

@@ -7,7 +7,7 @@ blots, ``cc.find_displacement`` -- for ALL sources in one kernel launch per cuto
 shape (the iterations are independent; nothing computed for source k feeds k+1 until
 the linear fit at align.py:720).
 
-``align_frames`` restates the loop around it (``align_images``, align.py:225-447) for affine maps: drizzle, find
+``align_frames`` restates the loop around it (``align_images``, align.py:225-447) for affine and polynomial maps: drizzle, find
 sources, re-drizzle without one frame, cut, blot, cross-correlate, fit, correct the frame's map.
 
 Not reproduced here (out of scope): the blotting itself
@@ -26,7 +26,7 @@ import numpy as np
 from . import _ffi, cc
 
 __all__ = ['find_linear_fit', 'iter_linear_fit', 'measure_shifts', 'measure_shifts_affine',
-           'usable_status', 'ST_SKIPPED', 'align_frames', 'compose_fit']
+           'usable_status', 'ST_SKIPPED', 'align_frames', 'compose_fit', 'shifted_poly_maps']
 
 # per-source status of the measurement: the library's SPX_ST_* codes (include/subpixal_hip.h) or
 ST_SKIPPED = -1          # cutout shape outside what the kernels take (3.._ffi.MAX_SIDE = 682 px per side): not measured
@@ -434,7 +434,16 @@ def compose_fit(affine, fit):
 
     Without WCS objects ``find_linear_fit`` fits G from 1-based image positions to where the blot puts the same
     content (``xyim -> xyim + dxy``), and the blot is the model ``M^-1(output)``: the content at image position p
-    belongs at output position ``M(G0(p))`` with ``G0(p) = G(p + 1) - 1`` in 0-based pixels."""
+    belongs at output position ``M(G0(p))`` with ``G0(p) = G(p + 1) - 1`` in 0-based pixels.
+
+    A ``resample.PolyMap`` comes back as the ``PolyMap`` ``M.compose(G0)`` of the same degree; a ``[6]`` map as a
+    ``[6]`` map."""
+    from .resample import PolyMap
+    if isinstance(affine, PolyMap):
+        f = np.asarray(fit['fit_matrix'], dtype=np.float64)
+        c = np.asarray(fit.get('center', np.zeros(2)), dtype=np.float64)
+        g = f @ (np.ones(2) - c) + c + np.asarray(fit['offset'], dtype=np.float64) - 1.0
+        return affine.compose(np.array([f[0, 0], f[0, 1], g[0], f[1, 0], f[1, 1], g[1]]))
     m = np.asarray(affine, dtype=np.float64)
     a, t = np.array([[m[0], m[1]], [m[3], m[4]]]), np.array([m[2], m[5]])
     f = np.asarray(fit['fit_matrix'], dtype=np.float64)
@@ -453,7 +462,10 @@ def _frame_catalogs(q, name, prim, margin, dtype):
     blotted median -- where the drizzle has one (``cr_reject=True``), else from the frame itself, as the
     reference's ``imfile if crclean_image is None else crclean_image`` (align.py:291-330)."""
     from .cutout import CutoutCatalog
+    from .resample import PolyMap
     m = q.map(name)
+    if isinstance(m, PolyMap):
+        return _frame_catalogs_poly(q, name, prim, margin, dtype, m)
     a, t = np.array([[m[0], m[1]], [m[3], m[4]]]), np.array([m[2], m[5]])
     ainv = np.linalg.inv(a)
     frame = q._resident(name).data
@@ -492,9 +504,67 @@ def _frame_catalogs(q, name, prim, margin, dtype):
     return img_cat, drz_cat, aff
 
 
+def shifted_poly_maps(m, centers, origins):
+    """``coef [N, 2, 21]``: the ``PolyMap`` ``m`` re-expanded about each of the N ``centers [N, 2]`` (frame pixels) with
+    ``origins [N, 2]`` (output pixels) subtracted from the result, in the convention of ``spx_blot_poly4_f32``.  All
+    sources at once: the binomial shift operator u^i v^j = sum C(i, a) C(j, b) sx^(i-a) sy^(j-b) u'^a v'^b applied
+    to the coefficient vector, with one loop over pairs of terms and none over sources."""
+    from math import comb
+    from .resample import POLY_TERMS, _TERMS, _slot
+    centers = np.asarray(centers, dtype=np.float64)
+    sx, sy = centers[:, 0] - m.center[0], centers[:, 1] - m.center[1]
+    px = [sx ** e for e in range(m.degree + 1)]
+    py = [sy ** e for e in range(m.degree + 1)]
+    out = np.zeros((len(centers), 2, POLY_TERMS))
+    for k, (i, j) in enumerate(_TERMS):
+        if i + j > m.degree or not m.coef[:, k].any():
+            continue
+        for a in range(i + 1):
+            for b in range(j + 1):
+                out[:, :, _slot(a, b)] += (comb(i, a) * comb(j, b) * px[i - a] * py[j - b])[:, None] * m.coef[:, k]
+    out[:, :, 0] -= np.asarray(origins, dtype=np.float64)
+    return out
+
+
+def _frame_catalogs_poly(q, name, prim, margin, dtype, m):
+    """:func:`_frame_catalogs` for a frame whose map is the ``PolyMap`` ``m``: the image boxes are the primary boxes'
+    corners through ``M^-1``, the bounding box taken outwards and grown by one pixel (the sagitta of a box edge
+    under a distortion of some per cent over thousands of pixels is far below that); ``ipos = M^-1(pos)``; the
+    per-source image-cutout -> drizzled-cutout maps are ``M`` re-expanded about each image cutout's centre with the
+    drizzled box's origin subtracted.  Returns ``(img_cat, drz_cat, coef [N, 2, 21], degree)`` for
+    ``find_linear_fit(poly=...)``."""
+    from .cutout import CutoutCatalog
+    frame = q._resident(name).data
+    fny, fnx = frame.shape
+    NY, NX = q.reference_image
+    b = prim.boxes.astype(np.float64)
+    cx = np.stack([b[:, 0], b[:, 0] + b[:, 2] - 1, b[:, 0], b[:, 0] + b[:, 2] - 1], axis=1)
+    cy = np.stack([b[:, 1], b[:, 1], b[:, 1] + b[:, 3] - 1, b[:, 1] + b[:, 3] - 1], axis=1)
+    ix, iy = m.inverse(cx, cy)
+    x0, x1 = np.floor(ix.min(axis=1)).astype(np.int64) - 1, np.ceil(ix.max(axis=1)).astype(np.int64) + 1
+    y0, y1 = np.floor(iy.min(axis=1)).astype(np.int64) - 1, np.ceil(iy.max(axis=1)).astype(np.int64) + 1
+    iboxes = np.stack([x0, y0, x1 - x0 + 1, y1 - y0 + 1], axis=1)
+    dboxes = prim.boxes.astype(np.int64) + np.array([-margin, -margin, 2 * margin, 2 * margin])
+    keep = (x0 >= 0) & (y0 >= 0) & (x1 < fnx) & (y1 < fny)
+    keep &= (dboxes[:, 0] >= 0) & (dboxes[:, 1] >= 0) & (dboxes[:, 0] + dboxes[:, 2] <= NX) & \
+            (dboxes[:, 1] + dboxes[:, 3] <= NY)
+    for bx in (iboxes, dboxes):
+        keep &= (bx[:, 2:].min(axis=1) >= 3) & (bx[:, 2:].max(axis=1) <= _ffi.MAX_SIDE)
+    iboxes, dboxes = iboxes[keep].astype(np.int32), dboxes[keep].astype(np.int32)
+    pos = prim.src_pos[keep]
+    ipos = np.stack(m.inverse(pos[:, 0], pos[:, 1]), axis=1)
+    wt = None if prim.src_weight is None else prim.src_weight[keep]
+    img_cat = CutoutCatalog(frame, iboxes, src_pos=ipos, src_id=prim.src_id[keep], dtype=dtype)
+    drz_cat = CutoutCatalog(q.output_sci, dboxes, src_pos=pos, src_weight=wt, src_id=prim.src_id[keep],
+                            mask=(q.output_wht == 0), segmentation_image=prim.segmentation_image, dtype=dtype)
+    centers = iboxes[:, :2] + 0.5 * (iboxes[:, 2:] - 1.0)
+    return img_cat, drz_cat, shifted_poly_maps(m, centers, dboxes[:, :2]), m.degree
+
+
 def align_frames(resample, catalog, nmax_iter=3, fitgeom='general', nclip=3, sigma=3.0, use_weights=True,
                  cc_type='NCC', pad=1, margin=None, history=False, min_shift=3e-3, timings=None):
-    """The reference's ``align_images`` loop (align.py:225-447) for affine maps, without WCS objects or files.
+    """The reference's ``align_images`` loop (align.py:225-447) for affine and polynomial maps, without WCS objects or
+    files.
 
     resample : :class:`subpixal_amd.resample.DeviceDrizzle`; its maps are corrected in place.
     catalog : :class:`subpixal_amd.catalogs.DeviceImageCatalog` (detection parameters, mask and filters set).
@@ -512,8 +582,9 @@ def align_frames(resample, catalog, nmax_iter=3, fitgeom='general', nclip=3, sig
     seconds per stage (``tools/bench_drizzle.py``), or None.
 
     Returns the list, per iteration, of ``{name: fit}``; with ``history`` each fit also carries ``'map_before'``,
-    ``'map_after'`` and ``'nsources'``.  Polynomial distortion, sky subtraction and FITS /
-    WCS write-back are out of scope.  Cosmic rays are rejected when ``resample`` was built with ``cr_reject=True``:
+    ``'map_after'`` and ``'nsources'`` (``[6]`` arrays, or ``resample.PolyMap`` objects for frames whose map is one:
+    any mix of affine and polynomial frames works, a polynomial frame's cutouts are blotted through the polynomial
+    maps of ``find_linear_fit(poly=...)``).  Sky subtraction and FITS / WCS write-back are out of scope.  Cosmic rays are rejected when ``resample`` was built with ``cr_reject=True``:
     the full ``execute()`` of every iteration makes the masks and the cleaned frames, the leave-one-out drizzles
     reuse the masks and the image cutouts come from the cleaned frames."""
     import time
@@ -548,10 +619,12 @@ def align_frames(resample, catalog, nmax_iter=3, fitgeom='general', nclip=3, sig
             q.fast_replace_image(name, previous)
             previous = name
             t0 = lap('leave_one_out', t0)
-            img_cat, drz_cat, aff = _frame_catalogs(q, name, prim, margin, dtype)
+            cats = _frame_catalogs(q, name, prim, margin, dtype)
+            img_cat, drz_cat = cats[:2]
+            how = dict(affine=cats[2]) if len(cats) == 3 else dict(poly=(cats[2], cats[3]))
             t0 = lap('catalogs', t0)
-            fit, _, _ = find_linear_fit(img_cat, drz_cat, affine=aff, fitgeom=fitgeom, nclip=nclip, sigma=sigma,
-                                        use_weights=use_weights, cc_type=cc_type)
+            fit, _, _ = find_linear_fit(img_cat, drz_cat, fitgeom=fitgeom, nclip=nclip, sigma=sigma,
+                                        use_weights=use_weights, cc_type=cc_type, **how)
             t0 = lap('find_linear_fit', t0)
             before = q.map(name)
             after = compose_fit(before, fit)

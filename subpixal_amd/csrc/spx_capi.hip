@@ -11,6 +11,7 @@
 #include "spx_detect_kernels.h"
 #include "spx_error_kernels.h"
 #include "spx_drizzle_kernels.h"
+#include "spx_drizzle_poly_kernels.h"
 #include "spx_crreject_kernels.h"
 #include "spx_deblend_kernels.h"
 #include "spx_background_kernels.h"
@@ -1203,6 +1204,26 @@ int drizzle(const void* rows, int nframes, int kernel, double fill, int out_ny, 
     return 0;
 }
 
+static_assert(sizeof(spx::DrizzlePolyRow) == SPX_DRIZZLE_POLY_ROW_BYTES, "include/subpixal_hip.h states the row size");
+// (subpixal_amd/_ffi.py names these offsets for the tools and tests that read a packed row)
+static_assert(offsetof(spx::DrizzlePolyRow, coef) == 40 && offsetof(spx::DrizzlePolyRow, xc) == 376 &&
+                  offsetof(spx::DrizzlePolyRow, inv) == 392 && offsetof(spx::DrizzlePolyRow, rx) == 424 &&
+                  offsetof(spx::DrizzlePolyRow, bx) == 456 && offsetof(spx::DrizzlePolyRow, degree) == 480,
+              "subpixal_amd/_ffi.py states the field offsets");
+template <typename T>
+int drizzle_poly(const void* rows, int nframes, int kernel, double fill, int out_ny, int out_nx, T* sci, float* wht,
+                 int32_t* ctx, void* stream) {
+    if (const int rc = drizzle_sizes(nframes, kernel, out_ny, out_nx)) return rc;
+    if (!rows || !sci || !wht || !ctx) return fail(SPX_E_ARG, "null pointer");
+    const int64_t tiles = (int64_t)((out_nx + spx::kDrzTileW - 1) / spx::kDrzTileW) *
+                          ((out_ny + spx::kDrzTileH - 1) / spx::kDrzTileH);
+    hipLaunchKernelGGL(spx::drizzle_poly_kernel<T>, dim3(capped_grid(tiles, 1 << 20)), dim3(256), 0,
+                       reinterpret_cast<hipStream_t>(stream), static_cast<const spx::DrizzlePolyRow*>(rows), nframes,
+                       kernel, fill, out_ny, out_nx, sci, wht, ctx);
+    SPX_HIP(hipGetLastError());
+    return 0;
+}
+
 // cosmic-ray rejection (spx_crreject_kernels.h)
 std::mutex g_crr_mu;
 std::set<std::pair<int, const void*>> g_crr_lds_ok;       // (device, kernel) whose dynamic-LDS limit is raised
@@ -1304,6 +1325,46 @@ int spx_drizzle_f32(const void* rows, int nframes, int kernel, double fill, int 
 int spx_drizzle_f64(const void* rows, int nframes, int kernel, double fill, int out_ny, int out_nx, double* out_sci,
                     float* out_wht, int32_t* out_ctx, void* stream) {
     return drizzle<double>(rows, nframes, kernel, fill, out_ny, out_nx, out_sci, out_wht, out_ctx, stream);
+}
+int spx_drizzle_poly_rows(const void* const* frames, const void* const* weights, const uint8_t* const* masks,
+                          const int32_t* shapes, const double* coef_f64, const int32_t* degree,
+                          const double* center_f64, const uint8_t* active, int nframes, double pixfrac, int kernel,
+                          int out_ny, int out_nx, void* out_rows) {
+    if (const int rc = drizzle_sizes(nframes, kernel, out_ny, out_nx)) return rc;
+    if (!(pixfrac > 0.0 && pixfrac <= 1.0)) return fail(SPX_E_ARG, "pixfrac must lie in (0, 1]");
+    if (!frames || !shapes || !coef_f64 || !degree || !center_f64 || !out_rows) return fail(SPX_E_ARG, "null pointer");
+    for (int k = 0; k < nframes; ++k) {
+        if (!frames[k]) return fail(SPX_E_ARG, "null pointer: frame " + std::to_string(k));
+        const int ny = shapes[2 * k], nx = shapes[2 * k + 1];
+        if (ny < 1 || nx < 1 || (int64_t)ny * nx >= 2147483647LL)
+            return fail(SPX_E_SHAPE, "frame " + std::to_string(k) + " must hold 1 .. 2^31 - 2 pixels");
+    }
+    std::vector<spx::DrizzlePolyRow> rows((size_t)nframes);
+    for (int k = 0; k < nframes; ++k) {
+        const int rc = spx::host::drizzle_poly_pack_row(
+            frames[k], weights ? weights[k] : nullptr, masks ? masks[k] : nullptr, shapes[2 * k], shapes[2 * k + 1],
+            active ? active[k] : 1, coef_f64 + (size_t)k * 2 * spx::kDrzPolyTerms, degree[k], center_f64 + 2 * k,
+            pixfrac, kernel, &rows[(size_t)k]);
+        const std::string which = "the map of frame " + std::to_string(k);
+        if (rc == 1) return fail(SPX_E_ARG, which + " has a coefficient or a centre that is not finite");
+        if (rc == 2)
+            return fail(SPX_E_ARG, which + " is singular: its Jacobian determinant is zero, not finite or changes "
+                                           "sign inside the frame");
+        if (rc == 3)
+            return fail(SPX_E_SHAPE, which + " shrinks or bends the frame so far that one output pixel gathers from "
+                                             "more than 8 x 8");
+        if (rc == 4) return fail(SPX_E_ARG, which + " has a degree outside 1 .. 5");
+    }
+    memcpy(out_rows, rows.data(), rows.size() * sizeof(spx::DrizzlePolyRow));  // nothing is written on an error
+    return 0;
+}
+int spx_drizzle_poly_f32(const void* rows, int nframes, int kernel, double fill, int out_ny, int out_nx, float* out_sci,
+                         float* out_wht, int32_t* out_ctx, void* stream) {
+    return drizzle_poly<float>(rows, nframes, kernel, fill, out_ny, out_nx, out_sci, out_wht, out_ctx, stream);
+}
+int spx_drizzle_poly_f64(const void* rows, int nframes, int kernel, double fill, int out_ny, int out_nx,
+                         double* out_sci, float* out_wht, int32_t* out_ctx, void* stream) {
+    return drizzle_poly<double>(rows, nframes, kernel, fill, out_ny, out_nx, out_sci, out_wht, out_ctx, stream);
 }
 int spx_drizzle_median_f32(const void* rows, int nframes, int nactive, int kernel, int nlow, int nhigh, int out_ny,
                            int out_nx, float* out_med, uint8_t* out_nmed, void* stream) {

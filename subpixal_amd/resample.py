@@ -1,14 +1,20 @@
 """Drizzle of dithered frames on the device, with the leave-one-out interface of the reference's ``Resample``
 (subpixal/resample.py) where that has a meaning without files, WCS objects and drizzlepac.
 
-``DeviceDrizzle`` holds K frames (CUDA tensors), one forward affine map per frame -- input pixel -> output pixel,
-``(X, Y) = (a0 x + a1 y + a2, a3 x + a4 y + a5)``, the ``[6]`` layout of ``blot.shift_affine`` -- and a fixed output
-grid.  ``execute()`` is one launch of the gather kernel of csrc/spx_drizzle_kernels.h (``spx_drizzle_f32`` /
-``_f64``); include/subpixal_hip.h carries the definition in full.  ``output_sci`` is the weighted MEAN of the input
+``DeviceDrizzle`` holds K frames (CUDA tensors), one forward map per frame -- input pixel -> output pixel, either
+affine, ``(X, Y) = (a0 x + a1 y + a2, a3 x + a4 y + a5)``, the ``[6]`` layout of ``blot.shift_affine``, or a
+:class:`PolyMap`, a bivariate polynomial of degree 1 .. 5 (instrument distortion) -- and a fixed output grid.
+``execute()`` is one launch of the gather kernel of csrc/spx_drizzle_kernels.h (``spx_drizzle_f32`` / ``_f64``);
+include/subpixal_hip.h carries the definition in full.  ``output_sci`` is the weighted MEAN of the input
 values that land on a pixel, i.e. input-pixel surface brightness: no ``scale**2`` is applied when the map changes the
 pixel area.  drizzlepac is not in the reference tree, so parity with it is UNPINNED (the definition is this
-library's own, after Fruchter & Hook 2002); polynomial distortion, sky subtraction and FITS input/output are not
-here.
+library's own, after Fruchter & Hook 2002); sky subtraction and FITS input/output are not here.
+
+With at least one ``PolyMap`` among the maps every row is packed by ``spx_drizzle_poly_rows`` (an affine entry
+becomes a degree-1 row) and ``execute()`` launches the gather of csrc/spx_drizzle_poly_kernels.h
+(``spx_drizzle_poly_f32`` / ``_f64``); with none nothing differs from the affine path, bit for bit.  Cosmic-ray
+rejection is not there for polynomial maps yet (its median and blot kernels read affine rows): ``cr_reject=True``
+together with a ``PolyMap`` is a ValueError.
 
 Cosmic-ray rejection (``cr_reject=True``; off by default, and with it off nothing differs from the plain drizzle) runs
 the steps of the reference's full ``execute()`` (resample.py:366-390) on the device: the median of the single-frame
@@ -22,15 +28,19 @@ The per-frame table the kernel reads lives on the device; ``set_map`` and droppi
 row.  Dropping only clears the frame's ``active`` flag, so the result is bit-identical to a fresh drizzle of the
 remaining frames in list order (``output_ctx`` numbers its bits by ``table_names``, dropped frames included).
 """
+from fractions import Fraction
+
 import numpy as np
 
 from . import _ffi
 
-__all__ = ['DeviceDrizzle', 'KERNELS', 'MAX_FRAMES']
+__all__ = ['DeviceDrizzle', 'PolyMap', 'KERNELS', 'MAX_FRAMES', 'MAX_DEGREE', 'POLY_TERMS']
 
 KERNELS = {'square': 0, 'turbo': 1, 'point': 2}            # SPX_DRIZZLE_SQUARE / _TURBO / _POINT
 _ROW_MASK = 16                                             # byte offset of a packed row's mask pointer (its third field)
 MAX_FRAMES = 128
+MAX_DEGREE = 5                                             # of a PolyMap
+POLY_TERMS = 21                                            # monomials u^i v^j with i + j <= 5 (blot.POLY_TERMS)
 _DTYPES = ('float32', 'float64')
 
 
@@ -38,7 +48,215 @@ def _dtype_name(a):
     return str(a.dtype).replace('torch.', '')
 
 
+def _slot(i, j):
+    """the slot of u^i v^j among the 21: k = d (d + 1) / 2 + (d - i), d = i + j (``spx_blot_poly4_f32``)"""
+    return (i + j) * (i + j + 1) // 2 + j
+
+
+_TERMS = [(d - j, j) for d in range(MAX_DEGREE + 1) for j in range(d + 1)]          # (i, j) of slot 0 .. 20
+
+
+def _pmul(p, q):
+    out = {}
+    for (i, j), a in p.items():
+        for (k, l), b in q.items():
+            out[i + k, j + l] = out.get((i + k, j + l), 0) + a * b
+    return out
+
+
+def _substitute(coef, degree, lu, lv):
+    """The coefficients [2, 21] of P(lu(u', v'), lv(u', v')) for the linear forms ``lu = (a, b, e)`` meaning
+    a u' + b v' + e (``lv`` likewise), in exact rational arithmetic: each result is rounded once."""
+    lu = {(1, 0): Fraction(lu[0]), (0, 1): Fraction(lu[1]), (0, 0): Fraction(lu[2])}
+    lv = {(1, 0): Fraction(lv[0]), (0, 1): Fraction(lv[1]), (0, 0): Fraction(lv[2])}
+    pu, pv = [{(0, 0): Fraction(1)}], [{(0, 0): Fraction(1)}]
+    for _ in range(degree):
+        pu.append(_pmul(pu[-1], lu))
+        pv.append(_pmul(pv[-1], lv))
+    out = np.zeros((2, POLY_TERMS))
+    mono = {}
+    for axis in range(2):
+        acc = {}
+        for k, (i, j) in enumerate(_TERMS):
+            if i + j > degree or coef[axis, k] == 0.0:
+                continue
+            if (i, j) not in mono:
+                mono[i, j] = _pmul(pu[i], pv[j])
+            c = Fraction(float(coef[axis, k]))
+            for key, val in mono[i, j].items():
+                acc[key] = acc.get(key, 0) + c * val
+        for (i, j), val in acc.items():
+            out[axis, _slot(i, j)] = float(val)
+    return out
+
+
+class PolyMap(object):
+    """``PolyMap(coef, degree, center=(0.0, 0.0))``: a forward map input pixel -> output pixel that is a bivariate
+    polynomial of total degree ``degree`` (1 .. 5) in ``u = x - xc, v = y - yc``,
+    ``X = sum_d sum_{i=d..0} coef[0][k] u^i v^(d-i)``, ``k = d (d + 1) / 2 + (d - i)``, ``Y`` with ``coef[1]``: the term
+    order and the 21 slots of ``spx_blot_poly4_f32`` / ``blot.poly_from_map``.  An immutable value object, host
+    float64 only; slots above ``degree`` are cleared."""
+    __slots__ = ('_coef', '_degree', '_center')
+
+    def __init__(self, coef, degree, center=(0.0, 0.0)):
+        if int(degree) != degree or not 1 <= int(degree) <= MAX_DEGREE:
+            raise ValueError("maps: the degree of a polynomial map must be 1 .. %d, got %r." % (MAX_DEGREE, degree))
+        degree = int(degree)
+        c = np.array(coef, dtype=np.float64)
+        n = (degree + 1) * (degree + 2) // 2
+        if c.ndim != 2 or c.shape[0] != 2 or not n <= c.shape[1] <= POLY_TERMS:
+            raise ValueError("maps: the coefficients of a polynomial map must have shape (2, 21), got %s."
+                             % (c.shape,))
+        full = np.zeros((2, POLY_TERMS))
+        full[:, :n] = c[:, :n]
+        center = np.array(center, dtype=np.float64)
+        if center.shape != (2,) or not np.all(np.isfinite(center)) or not np.all(np.isfinite(full)):
+            raise ValueError("maps: the coefficients and the centre of a polynomial map must be finite.")
+        full.setflags(write=False)
+        center.setflags(write=False)
+        object.__setattr__(self, '_coef', full)
+        object.__setattr__(self, '_degree', degree)
+        object.__setattr__(self, '_center', center)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("PolyMap is immutable.")
+
+    coef = property(lambda self: self._coef)
+    degree = property(lambda self: self._degree)
+    center = property(lambda self: self._center)
+
+    def __repr__(self):
+        return 'PolyMap(degree=%d, center=(%r, %r))' % (self._degree, self._center[0], self._center[1])
+
+    def _sum(self, x, y, du=0, dv=0):
+        u = np.asarray(x, dtype=np.float64) - self._center[0]
+        v = np.asarray(y, dtype=np.float64) - self._center[1]
+        out = [np.zeros(np.broadcast(u, v).shape), np.zeros(np.broadcast(u, v).shape)]
+        for k, (i, j) in enumerate(_TERMS):
+            if i + j > self._degree or i < du or j < dv:
+                continue
+            f = (i if du else 1) * (j if dv else 1)
+            term = f * u ** (i - du) * v ** (j - dv)
+            out[0] = out[0] + self._coef[0, k] * term
+            out[1] = out[1] + self._coef[1, k] * term
+        return out[0], out[1]
+
+    def __call__(self, x, y):
+        """``(X, Y)`` of the input positions ``(x, y)`` (arrays)"""
+        return self._sum(x, y)
+
+    def jacobian(self, x, y):
+        """``[..., 2, 2]``: ``[[dX/dx, dX/dy], [dY/dx, dY/dy]]`` at ``(x, y)``"""
+        xu, yu = self._sum(x, y, du=1)
+        xv, yv = self._sum(x, y, dv=1)
+        return np.stack([np.stack([xu, xv], axis=-1), np.stack([yu, yv], axis=-1)], axis=-2)
+
+    def inverse(self, X, Y, tol=1e-12, max_iter=50):
+        """``(x, y)`` with ``M(x, y) = (X, Y)`` by Newton from the linearisation at the centre, to ``tol`` px -- or to
+        16 ulps of the largest coordinate in play where that is more (7e-12 px at 4096): a float64 evaluation cannot
+        tell positions closer than that apart.  Raises ValueError if it does not converge."""
+        X, Y = np.broadcast_arrays(np.asarray(X, dtype=np.float64), np.asarray(Y, dtype=np.float64))
+        a = self.affine()
+        det = a[0] * a[4] - a[1] * a[3]
+        x = (a[4] * (X - a[2]) - a[1] * (Y - a[5])) / det
+        y = (-a[3] * (X - a[2]) + a[0] * (Y - a[5])) / det
+        for _ in range(int(max_iter)):
+            fx, fy = self(x, y)
+            j = self.jacobian(x, y)
+            d = j[..., 0, 0] * j[..., 1, 1] - j[..., 0, 1] * j[..., 1, 0]
+            rx, ry = fx - X, fy - Y
+            with np.errstate(all='ignore'):
+                dx = (j[..., 1, 1] * rx - j[..., 0, 1] * ry) / d
+                dy = (-j[..., 1, 0] * rx + j[..., 0, 0] * ry) / d
+            x, y = x - dx, y - dy
+            step = max(float(np.max(np.abs(dx), initial=0.0)), float(np.max(np.abs(dy), initial=0.0)))
+            if not np.isfinite(step):
+                break
+            size = max(float(np.max(np.abs(x), initial=1.0)), float(np.max(np.abs(y), initial=1.0)),
+                       float(np.max(np.abs(X), initial=1.0)), float(np.max(np.abs(Y), initial=1.0)))
+            if step <= max(tol, 16.0 * 2.0 ** -53 * size):
+                return x, y
+        raise ValueError("PolyMap.inverse: Newton's iteration did not converge to %g px." % tol)
+
+    def affine(self):
+        """the ``[6]`` linearisation at the centre"""
+        c, (xc, yc) = self._coef, self._center
+        return np.array([c[0, 1], c[0, 2], c[0, 0] - c[0, 1] * xc - c[0, 2] * yc,
+                         c[1, 1], c[1, 2], c[1, 0] - c[1, 1] * xc - c[1, 2] * yc])
+
+    def about(self, center):
+        """the same map re-expanded about another centre: exact rational arithmetic, each coefficient rounded once"""
+        center = np.asarray(center, dtype=np.float64)
+        sx = Fraction(float(center[0])) - Fraction(float(self._center[0]))
+        sy = Fraction(float(center[1])) - Fraction(float(self._center[1]))
+        return PolyMap(_substitute(self._coef, self._degree, (1, 0, sx), (0, 1, sy)), self._degree, center)
+
+    def compose(self, affine6):
+        """``M o G`` for the affine ``G(p) = (g0 x + g1 y + g2, g3 x + g4 y + g5)`` on the input side: a polynomial
+        of the same degree about the centre ``G^-1(centre)``, re-expanded exactly."""
+        g = np.asarray(affine6, dtype=np.float64)
+        if g.shape != (6,) or not np.all(np.isfinite(g)) or g[0] * g[4] - g[1] * g[3] == 0.0:
+            raise ValueError("compose: an invertible affine of six finite numbers.")
+        det = g[0] * g[4] - g[1] * g[3]
+        xc, yc = self._center
+        nc = np.array([(g[4] * (xc - g[2]) - g[1] * (yc - g[5])) / det, (-g[3] * (xc - g[2]) + g[0] * (yc - g[5])) / det])
+        f = [Fraction(float(v)) for v in g]
+        # u = G(p)_x - xc = g0 u' + g1 v' + (g0 nx + g1 ny + g2 - xc), the last term the rounding of the new centre
+        ex = f[0] * Fraction(float(nc[0])) + f[1] * Fraction(float(nc[1])) + f[2] - Fraction(float(xc))
+        ey = f[3] * Fraction(float(nc[0])) + f[4] * Fraction(float(nc[1])) + f[5] - Fraction(float(yc))
+        return PolyMap(_substitute(self._coef, self._degree, (f[0], f[1], ex), (f[3], f[4], ey)), self._degree, nc)
+
+    @classmethod
+    def from_affine(cls, a6, center=(0.0, 0.0)):
+        a = np.asarray(a6, dtype=np.float64)
+        if a.shape != (6,):
+            raise ValueError("maps: an affine map is six numbers (a0 a1 a2 a3 a4 a5).")
+        xc, yc = float(center[0]), float(center[1])
+        coef = np.zeros((2, POLY_TERMS))
+        coef[0, :3] = (a[0] * xc + a[1] * yc) + a[2], a[0], a[1]
+        coef[1, :3] = (a[3] * xc + a[4] * yc) + a[5], a[3], a[4]
+        return cls(coef, 1, (xc, yc))
+
+    @classmethod
+    def fit(cls, mapping, shape, degree=3, center=None):
+        """Least-squares fit of any callable ``(x, y) -> (X, Y)`` over a frame of ``shape = (ny, nx)``, about
+        ``center`` (default: the frame's centre).  Returns ``(map, max_residual_px)``; as ``blot.poly_from_map`` the
+        residual is taken on a finer probe grid (25 x 25 over the pixels' full extent) than the fit uses (17 x 17)."""
+        degree = int(degree)
+        if not 1 <= degree <= MAX_DEGREE:
+            raise ValueError("degree must be 1 .. %d." % MAX_DEGREE)
+        ny, nx = int(shape[0]), int(shape[1])
+        xc, yc = (0.5 * (nx - 1), 0.5 * (ny - 1)) if center is None else (float(center[0]), float(center[1]))
+        scale = 0.5 * max(nx, ny)                          # the design in u / scale: conditioned whatever the size
+
+        def grid(k):
+            gx, gy = np.meshgrid(np.linspace(-0.5, nx - 0.5, k), np.linspace(-0.5, ny - 0.5, k))
+            return gx.ravel(), gy.ravel()
+
+        def design(gx, gy):
+            u, v = (gx - xc) / scale, (gy - yc) / scale
+            return np.stack([u ** i * v ** j for i, j in _TERMS if i + j <= degree], axis=1)
+
+        gx, gy = grid(17)
+        X, Y = mapping(gx, gy)
+        dm = design(gx, gy)
+        cx, *_ = np.linalg.lstsq(dm, np.asarray(X, dtype=np.float64), rcond=None)
+        cy, *_ = np.linalg.lstsq(dm, np.asarray(Y, dtype=np.float64), rcond=None)
+        unscale = np.array([scale ** -(i + j) for i, j in _TERMS if i + j <= degree])
+        m = cls(np.stack([cx * unscale, cy * unscale]), degree, (xc, yc))
+        px, py = grid(25)
+        PX, PY = mapping(px, py)
+        mx, my = m(px, py)
+        return m, float(np.hypot(mx - PX, my - PY).max())
+
+
+def _is_poly(m):
+    return isinstance(m, PolyMap)
+
+
 def _check_map(m, what):
+    if _is_poly(m):
+        return m                                           # immutable, and checked when it was made
     m = np.asarray(m, dtype=np.float64)
     if m.shape != (6,) or not np.all(np.isfinite(m)):
         raise ValueError("maps: the map of %s must be six finite numbers (a0 a1 a2 a3 a4 a5)." % what)
@@ -60,7 +278,8 @@ class DeviceDrizzle(object):
     fill=0.0)``
 
     frames : sequence of K (1..128) 2-D arrays or tensors, all float32 or all float64; shapes may differ.
-    maps : ``[K, 6]`` forward affine maps, input pixel -> output pixel (0-based, pixel centres on integers).
+    maps : ``[K, 6]`` forward affine maps, input pixel -> output pixel (0-based, pixel centres on integers), or a
+        sequence of K entries, each a ``[6]`` array or a :class:`PolyMap`.
     out_shape : ``(NY, NX)`` of the output grid (``reference_image``); it never changes.
     names : K distinct hashable names (default ``0 .. K-1``).
     weights : None, or per frame None (weight 1) or a map of the frame's shape, >= 0; a pixel that is masked, not
@@ -88,9 +307,14 @@ class DeviceDrizzle(object):
         names = list(range(K)) if names is None else list(names)
         if len(names) != K or len(set(names)) != K:
             raise ValueError("names: one distinct name per frame.")
-        maps = np.asarray(maps, dtype=np.float64)
-        if maps.shape != (K, 6):
-            raise ValueError("maps: expected shape (%d, 6), got %s." % (K, maps.shape))
+        if not isinstance(maps, np.ndarray) and any(_is_poly(m) for m in maps):
+            maps = list(maps)
+            if len(maps) != K:
+                raise ValueError("maps: expected %d maps, got %d." % (K, len(maps)))
+        else:
+            maps = np.asarray(maps, dtype=np.float64)
+            if maps.shape != (K, 6):
+                raise ValueError("maps: expected shape (%d, 6), got %s." % (K, maps.shape))
         weights = K * [None] if weights is None else list(weights)
         masks = K * [None] if masks is None else list(masks)
         if len(weights) != K:
@@ -130,6 +354,7 @@ class DeviceDrizzle(object):
                                    driz_cr_snr=driz_cr_snr, driz_cr_scale=driz_cr_scale)
         self._rows_host = None                         # uint8 [K][ROW_BYTES], as spx_drizzle_rows packed them
         self._rows_dev = None
+        self._rows_poly = False                        # the rows are spx_drizzle_poly_rows' (a PolyMap among the maps)
         self._stale = True                             # the whole table must be packed again
         self.output_sci = self.output_wht = self.output_ctx = None
         self.output_median = self.output_nmedian = self.output_crmask = self.output_crclean = None
@@ -196,6 +421,7 @@ class DeviceDrizzle(object):
         if cr_reject is not None:
             cr['on'] = bool(cr_reject)
         if cr['on']:
+            self._no_poly_with_cr(self._maps.values())
             if cr['rms'] is None:
                 raise ValueError("rms: cr_reject needs the frames' noise (a scalar, or per frame a scalar or a map).")
             if min(self._out_shape) < 6:
@@ -238,17 +464,39 @@ class DeviceDrizzle(object):
         or None when the last full ``execute()`` made none"""
         return self._crclean.get(name)
 
+    @staticmethod
+    def _no_poly_with_cr(maps):
+        if any(_is_poly(m) for m in maps):
+            raise ValueError("cr_reject: cosmic-ray rejection is not available for polynomial maps (PolyMap) yet: its "
+                             "median and blot kernels read affine rows.")
+
+    def _poly(self):
+        return any(_is_poly(m) for m in self._maps.values())
+
     def map(self, name):
-        return self._maps[name].copy()
+        """the map of frame ``name`` as it was set: a copy of the ``[6]`` array, or the (immutable) ``PolyMap``"""
+        m = self._maps[name]
+        return m if _is_poly(m) else m.copy()
 
     def set_map(self, name, affine):
-        """Replace the map of frame ``name`` (listed or dropped); one row of the device table is rewritten."""
+        """Replace the map of frame ``name`` (listed or dropped) by a ``[6]`` affine or a ``PolyMap``; one row of the
+        device table is rewritten (the whole table when the first ``PolyMap`` arrives or the last one leaves: the two
+        kinds of row differ).  A map the packing refuses leaves everything as it was."""
         if name not in self._maps:
             raise ValueError("set_map: no frame named %r." % (name,))
         old = self._maps[name]
-        self._maps[name] = _check_map(affine, repr(name))
+        new = _check_map(affine, repr(name))
+        if self._cr['on']:
+            self._no_poly_with_cr([new])
+        self._maps[name] = new
         try:
-            self._rewrite_row(name)
+            if self._poly() != self._rows_poly and self._rows_dev is not None and not self._stale:
+                # the kind of row flips for EVERY frame, and the two packings size their windows differently: the
+                # whole table is packed here, so that whatever is refused is refused before anything changes
+                self._pack(self._order)
+                self._stale = True
+            else:
+                self._rewrite_row(name)
         except ValueError:                             # what the packing refuses (the 8 x 8 window): nothing changes
             self._maps[name] = old
             raise
@@ -259,7 +507,7 @@ class DeviceDrizzle(object):
         c = object.__new__(DeviceDrizzle)
         c.__dict__.update(self.__dict__)
         c._pool = dict(self._pool)                     # the _Frame objects (and their tensors) are shared
-        c._maps = {n: m.copy() for n, m in self._maps.items()}
+        c._maps = {n: m if _is_poly(m) else m.copy() for n, m in self._maps.items()}
         c._order = list(self._order)
         c._active = dict(self._active)
         c._rows_host = None if self._rows_host is None else self._rows_host.copy()
@@ -333,12 +581,24 @@ class DeviceDrizzle(object):
               for n, f in zip(names, fr)]
         masks = np.array([0 if m is None else m.data_ptr() for m in mk], np.uint64)
         shapes = np.array([tuple(f.data.shape) for f in fr], np.int32)
-        maps = np.ascontiguousarray(np.stack([self._maps[n] for n in names]))
         active = np.array([self._active[n] for n in names], np.uint8)
-        rows = np.zeros((K, _ffi.DRIZZLE_ROW_BYTES), np.uint8)
-        rc = lib.spx_drizzle_rows(frames.ctypes.data, weights.ctypes.data, masks.ctypes.data, shapes.ctypes.data,
-                                  maps.ctypes.data, active.ctypes.data, K, self._pixfrac, KERNELS[self._kernel],
-                                  self._out_shape[0], self._out_shape[1], rows.ctypes.data)
+        if self._poly():
+            pm = [m if _is_poly(m) else PolyMap.from_affine(m) for m in (self._maps[n] for n in names)]
+            coef = np.ascontiguousarray(np.stack([m.coef for m in pm]))
+            degree = np.array([m.degree for m in pm], np.int32)
+            center = np.ascontiguousarray(np.stack([m.center for m in pm]))
+            rows = np.zeros((K, _ffi.DRIZZLE_POLY_ROW_BYTES), np.uint8)
+            rc = lib.spx_drizzle_poly_rows(frames.ctypes.data, weights.ctypes.data, masks.ctypes.data,
+                                           shapes.ctypes.data, coef.ctypes.data, degree.ctypes.data,
+                                           center.ctypes.data, active.ctypes.data, K, self._pixfrac,
+                                           KERNELS[self._kernel], self._out_shape[0], self._out_shape[1],
+                                           rows.ctypes.data)
+        else:
+            maps = np.ascontiguousarray(np.stack([self._maps[n] for n in names]))
+            rows = np.zeros((K, _ffi.DRIZZLE_ROW_BYTES), np.uint8)
+            rc = lib.spx_drizzle_rows(frames.ctypes.data, weights.ctypes.data, masks.ctypes.data, shapes.ctypes.data,
+                                      maps.ctypes.data, active.ctypes.data, K, self._pixfrac, KERNELS[self._kernel],
+                                      self._out_shape[0], self._out_shape[1], rows.ctypes.data)
         if rc in (_ffi.E_ARG, _ffi.E_SHAPE):
             raise ValueError(lib.spx_last_error().decode())
         _ffi.check(rc)
@@ -374,15 +634,19 @@ class DeviceDrizzle(object):
         elif not self._cr['on'] and self._merged:
             self._crmask, self._merged, self._crclean = {}, {}, {}
             self._stale = True
-        if self._stale or self._rows_dev is None:
+        if self._stale or self._rows_dev is None or self._rows_poly != self._poly():
             self._rows_host = self._pack(self._order)
             self._rows_dev = torch.from_numpy(self._rows_host).cuda()
+            self._rows_poly = self._poly()
             self._stale = False
         dev = self._rows_dev.device
         sci = torch.empty((NY, NX), dtype=torch.float32 if self._dtype == 'float32' else torch.float64, device=dev)
         wht = torch.empty((NY, NX), dtype=torch.float32, device=dev)
         ctx = torch.empty(((K + 31) // 32, NY, NX), dtype=torch.int32, device=dev)
-        fn = lib.spx_drizzle_f32 if self._dtype == 'float32' else lib.spx_drizzle_f64
+        if self._rows_poly:
+            fn = lib.spx_drizzle_poly_f32 if self._dtype == 'float32' else lib.spx_drizzle_poly_f64
+        else:
+            fn = lib.spx_drizzle_f32 if self._dtype == 'float32' else lib.spx_drizzle_f64
         _ffi.check(fn(self._rows_dev.data_ptr(), K, KERNELS[self._kernel], self._fill, NY, NX, sci.data_ptr(),
                       wht.data_ptr(), ctx.data_ptr(), device.stream_ptr()))
         self.output_sci, self.output_wht, self.output_ctx = sci, wht, ctx

@@ -40,6 +40,8 @@
  *   spx_drizzle_median_f32 / _f64, spx_drizzle_cr_f32 / _f64
  *                               <-  the cosmic-ray rejection of the same execute() (resample.py:366-390): median,
  *                                   blot back, derivative, drizCR; parity with drizzlepac UNPINNED.
+ *   spx_sky_stats_f32 / _f64    <-  sky.subtractSky in front of the same execute() (resample.py:359-364): the
+ *                                   sigma-clipped level of every whole frame; parity with drizzlepac UNPINNED.
  *   spx_blot_affine4_f32        <-  the four blot_cutout(dzct, imct) calls per source of
  *                                   subpixal/align.py:664-676 (blot.py:79-155, drizzlepac
  *                                   tblot, interp='poly5') for coordinate maps that are
@@ -778,7 +780,8 @@ int spx_drizzle_poly_f64(const void* rows, int nframes, int kernel, double fill,
  *   6. Mask.  crmask(i, j) = fail_2(i, j) and (some pixel of the 3 x 3 block around (i, j) has fail_1).
  *      clean(i, j) = b cast to the frame dtype where crmask is 1; elsewhere d, unchanged, NaNs included.
  *   drizzlepac's defaults: snr = (3.5, 3.0), scale = (1.2, 0.7), nlow = nhigh = 0, sky = 0, no gain.
- *   Not here: minmed and the other combine types, driz_cr_grow and the CTE tail, static masks, sky subtraction.
+ *   Not here: minmed and the other combine types, driz_cr_grow and the CTE tail, static masks.  The frames are taken
+ *   as they are: a caller whose frames differ in sky level subtracts it first (spx_sky_stats_* below).
  *
  * Both entries take the DEVICE table spx_drizzle_rows packed and only launch, as spx_drizzle_* do; neither has an
  * atomic or depends on the grid, so every output is the same bit pattern on every run.  They can be captured, with
@@ -817,6 +820,74 @@ int spx_drizzle_cr_f64(const void* rows, int nframes, int frame, int fny, int fn
                        const uint8_t* nmed, int out_ny, int out_nx, double rms_scalar, const double* rms_map,
                        double sky, double gain, double snr1, double snr2, double scale1, double scale2,
                        uint8_t* out_crmask, double* out_clean, void* stream);
+
+/*
+ * Sigma-clipped statistics of WHOLE frames: the sky level that resample.DeviceDrizzle (skysub=True) subtracts from
+ * each frame before the drizzle, where the reference runs sky.subtractSky (resample.py:359-364).  The library's own
+ * definition, in the spirit of drizzlepac's skystat / skyclip / skylsigma / skyusigma / skylower / skyupper;
+ * drizzlepac is not in the reference tree, so parity with it is UNPINNED, as for the rest of the drizzle.  It is the
+ * mesh-cell rule of spx_background_mesh_* (steps 1-4 there) over all usable pixels of a frame, with separate lower
+ * and upper clip factors and optional hard bounds.
+ *
+ * A pixel is USABLE when its value is finite, its mask byte is 0 (or there is no mask), its weight (where a weight
+ * map is given) is finite and > 0, and lower <= v <= upper for each bound that is given (a NaN bound: none).
+ * n_usable is their count.  The closed range [lo, hi] starts at the hard bounds (-inf / +inf where there is none).
+ * Rounds r = 0 .. max_iters:
+ *   1. n = the count of usable values in [lo, hi].  n == 0: stop, status SPX_SKY_EMPTY; sky, med, mean and std are
+ *      NaN (possible only in round 0).
+ *   2. med = the exact median of those values (even count: (a + b) * 0.5 of the two middle values, in float64).
+ *   3. min == max over those values: mean = that value, std = 0, stop.  Otherwise, in float64 with contraction off,
+ *      S1 = sum(v - med), S2 = sum((v - med)^2), mean = med + S1 / n, std = sqrt(max(S2 / n - (S1 / n)^2, 0)).
+ *      THE ORDER OF THE TWO SUMS IS FIXED and does not depend on the device, its CU count or on scheduling: number
+ *      the frame's pixels i = y * nx + x.  4096 accumulators j = 0 .. 4095, each starting from 0.0, add the terms
+ *      of the pixels j, j + 4096, j + 8192, ... in that order (pixels outside the range are skipped).  Accumulators
+ *      64 g .. 64 g + 63 are then added by a butterfly: for m = 32, 16, 8, 4, 2, 1 every accumulator becomes
+ *      itself + its partner (index ^ m); the 64 results g = 0 .. 63 are added four at a time in order of g starting
+ *      from 0.0 (0.0 + s_4q + s_4q+1 + s_4q+2 + s_4q+3, q = 0 .. 15), and these 16 in order of q starting from 0.0.
+ *   4. Stop if std is not > 0 or r == max_iters.
+ *   5. lo' = max(lo, med - lsigma * std), hi' = min(hi, med + usigma * std), each product and sum rounded on its own.
+ *      If the count inside [lo', hi'] equals n: stop.  If it is 0 (factors < 1): keep the old range and stop.
+ *      Otherwise [lo, hi] = [lo', hi'] and go to 1.
+ * Results per frame: med, mean, std, lo, hi of the last round whose statistics were computed, n_usable, n_final = n of
+ * that round, rounds = the number of rounds whose statistics were computed, status, and
+ *   sky = med (SPX_SKY_MEDIAN), mean (SPX_SKY_MEAN), or for SPX_SKY_MODE the mesh rule: mean if std == 0,
+ *   2.5 med - 1.5 mean if |mean - med| < 0.3 std, else med.
+ * -0.0 counts as +0.0; the sign of a zero result is not part of the definition.
+ *
+ * The median is found by radix selection over the order-preserving integer image of the values (integer histograms:
+ * exact and independent of scheduling), so every result is the same bit pattern on every run and every device.
+ *
+ * spx_sky_stats_f32 / _f64 -- all frames in one launch sequence; the call only enqueues (one memset and
+ * (max_iters + 1) (2 D + 2) + 2 kernels, D = 3 / 6 digits for float32 / float64), copies nothing to the host and can
+ * be captured.  Each frame is read (max_iters + 1) (D + 1) times at most; a frame that has stopped is not read again.
+ *   frames, weights, masks : DEVICE arrays of nframes device pointers (frames in the call's dtype, weights in the
+ *              same dtype, masks uint8, nonzero = bad), each frame row-major [ny][nx] and contiguous.  weights and
+ *              masks may be NULL as a whole, and each of their entries may be NULL.
+ *   shapes   : DEVICE int32 [nframes][2] = (ny, nx).  A frame with a side < 1, 2^31 - 1 pixels or more, or a NULL
+ *              frame pointer gets status SPX_SKY_BAD_FRAME and NaN statistics: shapes cannot be checked without a copy.
+ *   lower, upper : hard bounds, NaN = none;  lsigma, usigma : clip factors;  max_iters : clipping rounds after round 0
+ *   stat     : SPX_SKY_MEDIAN, SPX_SKY_MEAN or SPX_SKY_MODE
+ *   work     : spx_sky_workspace_bytes(nframes) bytes (0 for nframes outside 1 .. 128), 8-byte aligned; too small or
+ *              NULL: SPX_E_WORKSPACE
+ *   out      : float64 [nframes][6] = sky, med, mean, std, lo, hi
+ *   out_counts : int64 [nframes][2] = n_usable, n_final;  out_status : int32 [nframes][2] = status bits, rounds
+ *   SPX_E_ARG: a null table (frames, shapes) or output, nframes outside 1 .. 128, lsigma or usigma not positive and
+ *   finite, max_iters < 0 or > 1000, unknown stat, lower > upper.  Everything is checked before any HIP call.
+ */
+#define SPX_SKY_MEDIAN 0
+#define SPX_SKY_MEAN 1
+#define SPX_SKY_MODE 2
+#define SPX_SKY_EMPTY 1     /* status bit: no usable pixel */
+#define SPX_SKY_BAD_FRAME 2 /* status bit: a side < 1, too many pixels, or a NULL frame */
+size_t spx_sky_workspace_bytes(int nframes);
+int spx_sky_stats_f32(const void* const* frames, const void* const* weights, const uint8_t* const* masks,
+                      const int32_t* shapes, int nframes, double lower, double upper, double lsigma, double usigma,
+                      int max_iters, int stat, void* work, size_t work_bytes, double* out, int64_t* out_counts,
+                      int32_t* out_status, void* stream);
+int spx_sky_stats_f64(const void* const* frames, const void* const* weights, const uint8_t* const* masks,
+                      const int32_t* shapes, int nframes, double lower, double upper, double lsigma, double usigma,
+                      int max_iters, int stat, void* work, size_t work_bytes, double* out, int64_t* out_counts,
+                      int32_t* out_status, void* stream);
 
 /*
  * Synthetic Gaussian-spot pairs: pair k = first_index + i has

@@ -12,7 +12,8 @@ from .utils import py2round
 from . import detect                                         # noqa: F401  (source finding)
 from . import catalogs                                       # noqa: F401  (catalogue selection)
 from . import resample                                       # noqa: F401  (drizzle of dithered frames)
+from . import sky                                            # noqa: F401  (whole-frame sky statistics)
 
 __version__ = '0.1.0'
 __all__ = ['find_displacement', 'find_displacement_batch', 'find_displacement_var', 'xcorr_refine_batch',
-           'find_peak', 'find_peak_batch', 'py2round', 'detect', 'catalogs', 'resample']
+           'find_peak', 'find_peak_batch', 'py2round', 'detect', 'catalogs', 'resample', 'sky']

@@ -20,6 +20,9 @@ DRIZZLE_POLY_ROW_BYTES = 488                             # SPX_DRIZZLE_POLY_ROW_
 DRIZZLE_POLY_ROW_COEF, DRIZZLE_POLY_ROW_CENTER, DRIZZLE_POLY_ROW_INV = 40, 376, 392
 DRIZZLE_POLY_ROW_WINDOW, DRIZZLE_POLY_ROW_DROP, DRIZZLE_POLY_ROW_DEGREE = 424, 456, 480
 E_ARG, E_SHAPE = -1, -2                                  # SPX_E_ARG, SPX_E_SHAPE
+E_WORKSPACE = -4                                         # SPX_E_WORKSPACE
+SKY_STATS = {'median': 0, 'mean': 1, 'mode': 2}          # SPX_SKY_MEDIAN / _MEAN / _MODE
+SKY_EMPTY, SKY_BAD_FRAME = 1, 2                          # SPX_SKY_EMPTY, SPX_SKY_BAD_FRAME
 REFINE_DEFAULT, REFINE_F64, REFINE_F32 = 0, 1, 2         # SPX_REFINE_* (include/subpixal_hip.h)
 MAX_SIDE = 682
 MAX_UPSAMPLE = 59
@@ -140,6 +143,13 @@ _SIGNATURES = {
                                            _c.c_int, _c.c_double, _vp, _c.c_size_t, _vp, _vp, _vp, _vp, _vp]),
     'spx_background_maps_f64': (_c.c_int, [_vp, _vp, _vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
                                            _c.c_int, _c.c_double, _vp, _c.c_size_t, _vp, _vp, _vp, _vp, _vp]),
+    # whole-frame sigma-clipped statistics (spx_sky_stats_*): DEVICE tables frames, weights, masks, shapes; nframes,
+    # lower, upper, lsigma, usigma, max_iters, stat, work, work_bytes, out, out_counts, out_status, stream
+    'spx_sky_workspace_bytes': (_c.c_size_t, [_c.c_int]),
+    'spx_sky_stats_f32': (_c.c_int, [_vp, _vp, _vp, _vp, _c.c_int, _c.c_double, _c.c_double, _c.c_double, _c.c_double,
+                                     _c.c_int, _c.c_int, _vp, _c.c_size_t, _vp, _vp, _vp, _vp]),
+    'spx_sky_stats_f64': (_c.c_int, [_vp, _vp, _vp, _vp, _c.c_int, _c.c_double, _c.c_double, _c.c_double, _c.c_double,
+                                     _c.c_int, _c.c_int, _vp, _c.c_size_t, _vp, _vp, _vp, _vp]),
     'spx_blot_affine4_f32': (_c.c_int, [_vp, _c.c_int64, _c.c_int, _c.c_int, _vp, _vp, _c.c_int,
                                         _c.c_int, _vp, _vp]),
     'spx_blot_poly4_f32': (_c.c_int, [_vp, _c.c_int64, _c.c_int, _c.c_int, _vp, _c.c_int, _vp, _c.c_int,

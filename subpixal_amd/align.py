@@ -468,7 +468,7 @@ def _frame_catalogs(q, name, prim, margin, dtype):
         return _frame_catalogs_poly(q, name, prim, margin, dtype, m)
     a, t = np.array([[m[0], m[1]], [m[3], m[4]]]), np.array([m[2], m[5]])
     ainv = np.linalg.inv(a)
-    frame = q._resident(name).data
+    frame = q.science(name) if hasattr(q, 'science') else q._resident(name).data     # frame - sky with skysub
     if q.crclean(name) is not None:                 # align.py:330: the CR-cleaned frame where there is one
         frame = q.crclean(name)
     fny, fnx = frame.shape
@@ -534,7 +534,7 @@ def _frame_catalogs_poly(q, name, prim, margin, dtype, m):
     drizzled box's origin subtracted.  Returns ``(img_cat, drz_cat, coef [N, 2, 21], degree)`` for
     ``find_linear_fit(poly=...)``."""
     from .cutout import CutoutCatalog
-    frame = q._resident(name).data
+    frame = q.science(name) if hasattr(q, 'science') else q._resident(name).data     # frame - sky with skysub
     fny, fnx = frame.shape
     NY, NX = q.reference_image
     b = prim.boxes.astype(np.float64)

@@ -15,6 +15,7 @@
 #include "spx_crreject_kernels.h"
 #include "spx_deblend_kernels.h"
 #include "spx_background_kernels.h"
+#include "spx_sky_kernels.h"
 #include "spx_tables.h"
 #include "../../include/subpixal_hip.h"
 
@@ -1698,6 +1699,93 @@ int spx_background_maps_f64(const double* mesh_bkg, const double* mesh_rms, cons
                             void* stream) {
     return background_maps<double>(mesh_bkg, mesh_rms, mesh_ngood, ncy, ncx, bh, bw, filter_size, fny, fnx, nsigma,
                                    work, work_bytes, bkg_out, rms_out, thr_out, status, stream);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------
+// sigma-clipped statistics of whole frames (spx_sky_kernels.h).  Workspace: [nframes] state records, the frames'
+// histograms, the moment partials; cleared by the call.  The call only enqueues: a memset and kernels.
+// ---------------------------------------------------------------------------------------------------------
+namespace {
+template <typename T>
+int sky_stats(const void* const* frames, const void* const* weights, const uint8_t* const* masks,
+              const int32_t* shapes, int nframes, double lower, double upper, double lsigma, double usigma,
+              int max_iters, int stat, void* work, size_t work_bytes, double* out, int64_t* out_counts,
+              int32_t* out_status, void* stream) {
+    if (!frames || !shapes) return fail(SPX_E_ARG, "null table (frames, shapes)");
+    if (!out || !out_counts || !out_status) return fail(SPX_E_ARG, "null output");
+    if (nframes < 1 || nframes > spx::kSkyMaxFrames) return fail(SPX_E_ARG, "nframes must be 1..128");
+    if (!(lsigma > 0.0) || !(lsigma - lsigma == 0.0) || !(usigma > 0.0) || !(usigma - usigma == 0.0))
+        return fail(SPX_E_ARG, "lsigma and usigma must be positive and finite");
+    if (max_iters < 0) return fail(SPX_E_ARG, "max_iters must not be negative");
+    if (stat != SPX_SKY_MEDIAN && stat != SPX_SKY_MEAN && stat != SPX_SKY_MODE)
+        return fail(SPX_E_ARG, "stat must be SPX_SKY_MEDIAN, SPX_SKY_MEAN or SPX_SKY_MODE");
+    if (lower > upper) return fail(SPX_E_ARG, "lower must not exceed upper");
+    if (max_iters > 1000) return fail(SPX_E_ARG, "max_iters must not exceed 1000");
+    const size_t need = (size_t)nframes * spx::kSkyFrameBytes;
+    if (!work || work_bytes < need)
+        return fail(SPX_E_WORKSPACE, "workspace missing or smaller than spx_sky_workspace_bytes(nframes)");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const T* const* fr = reinterpret_cast<const T* const*>(frames);
+    const T* const* wt = reinterpret_cast<const T* const*>(weights);
+    int gpf = 2048 / nframes;                       // hist workgroups per frame: free (integer sums)
+    gpf = gpf < 16 ? 16 : (gpf > 512 ? 512 : gpf);
+    SPX_HIP(hipMemsetAsync(work, 0, need, s));
+    hipError_t err = hipSuccess;
+    spx::host::sky_stats_launch(spx::SkyKey<T>::digits, max_iters, [&](int kind, int pass, int round) {
+        if (err != hipSuccess) return;
+        switch (kind) {
+        case 0:
+            hipLaunchKernelGGL(spx::sky_init_kernel, dim3(1), dim3(256), 0, s, frames, shapes, nframes, lower, upper,
+                               work);
+            break;
+        case 1:
+            hipLaunchKernelGGL(spx::sky_hist_kernel<T>, dim3((unsigned)(nframes * gpf)), dim3(256),
+                               spx::kSkyHistLdsBytes, s, fr, wt, masks, shapes, nframes, gpf, pass, work);
+            break;
+        case 2:
+            hipLaunchKernelGGL(spx::sky_select_kernel<T>, dim3((unsigned)nframes), dim3(256), spx::kSkySelectLdsBytes,
+                               s, nframes, pass, round, work);
+            break;
+        case 3:
+            hipLaunchKernelGGL(spx::sky_moments_kernel<T>, dim3((unsigned)(nframes * spx::kSkyMomentGrid)), dim3(256),
+                               spx::kSkyMomentLdsBytes, s, fr, wt, masks, shapes, nframes, work);
+            break;
+        case 4:
+            hipLaunchKernelGGL(spx::sky_finish_kernel, dim3(1), dim3(256), 0, s, nframes, round, max_iters, lsigma,
+                               usigma, work);
+            break;
+        default:
+            hipLaunchKernelGGL(spx::sky_output_kernel, dim3(1), dim3(256), 0, s, nframes, stat, (const void*)work, out,
+                               reinterpret_cast<long long*>(out_counts), out_status);
+        }
+        err = hipGetLastError();
+    });
+    SPX_HIP(err);
+    return 0;
+}
+}  // namespace
+
+extern "C" {
+
+size_t spx_sky_workspace_bytes(int nframes) {
+    if (nframes < 1 || nframes > spx::kSkyMaxFrames) return 0;
+    return (size_t)nframes * spx::kSkyFrameBytes;
+}
+int spx_sky_stats_f32(const void* const* frames, const void* const* weights, const uint8_t* const* masks,
+                      const int32_t* shapes, int nframes, double lower, double upper, double lsigma, double usigma,
+                      int max_iters, int stat, void* work, size_t work_bytes, double* out, int64_t* out_counts,
+                      int32_t* out_status, void* stream) {
+    return sky_stats<float>(frames, weights, masks, shapes, nframes, lower, upper, lsigma, usigma, max_iters, stat,
+                            work, work_bytes, out, out_counts, out_status, stream);
+}
+int spx_sky_stats_f64(const void* const* frames, const void* const* weights, const uint8_t* const* masks,
+                      const int32_t* shapes, int nframes, double lower, double upper, double lsigma, double usigma,
+                      int max_iters, int stat, void* work, size_t work_bytes, double* out, int64_t* out_counts,
+                      int32_t* out_status, void* stream) {
+    return sky_stats<double>(frames, weights, masks, shapes, nframes, lower, upper, lsigma, usigma, max_iters, stat,
+                             work, work_bytes, out, out_counts, out_status, stream);
 }
 
 }  // extern "C"

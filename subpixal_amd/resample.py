@@ -8,7 +8,17 @@ affine, ``(X, Y) = (a0 x + a1 y + a2, a3 x + a4 y + a5)``, the ``[6]`` layout of
 include/subpixal_hip.h carries the definition in full.  ``output_sci`` is the weighted MEAN of the input
 values that land on a pixel, i.e. input-pixel surface brightness: no ``scale**2`` is applied when the map changes the
 pixel area.  drizzlepac is not in the reference tree, so parity with it is UNPINNED (the definition is this
-library's own, after Fruchter & Hook 2002); sky subtraction and FITS input/output are not here.
+library's own, after Fruchter & Hook 2002); FITS input/output is not here.
+
+Sky subtraction (``skysub=True``; off by default, and with it off nothing differs: no new tensor, no new launch, the
+same row bytes) stands where the reference runs ``sky.subtractSky`` (resample.py:359-364): the first full
+``execute()`` computes every listed frame's sigma-clipped level in one call of ``sky.frame_stats``'s kernels
+(csrc/spx_sky_kernels.h) over the frame's own mask and weight, keeps it as ``computed_sky`` and FREEZES it, as the
+reference's sky file does for its leave-one-out drizzles (resample.py:586-597).  The drizzle, the median, the
+comparison and ``crclean`` then read ``frame - T(sky)``, one IEEE subtraction in the frame's dtype made on the device
+into a second tensor (``science(name)``); the frame as given is kept.  The definition is the library's own
+(include/subpixal_hip.h, sky block), parity with drizzlepac UNPINNED; its ``'match'`` methods, the static mask and
+its histogram mode are not here.
 
 With at least one ``PolyMap`` among the maps every row is packed by ``spx_drizzle_poly_rows`` (an affine entry
 becomes a degree-1 row) and ``execute()`` launches the gather of csrc/spx_drizzle_poly_kernels.h
@@ -293,13 +303,21 @@ class DeviceDrizzle(object):
     combine_nlow, combine_nhigh : values dropped from the median at either end where that leaves one.
     driz_cr_snr, driz_cr_scale : the two thresholds, ``(3.5, 3.0)`` and ``(1.2, 0.7)``; the second pair must not exceed
         the first.
-    ``set_config_parameters`` takes the same eight keywords; per-frame values are in the order of ``names``.
+    skysub : subtract each frame's sky level before everything else (default False).  With it ``sky`` must stay None.
+    skystat ('median' | 'mean' | 'mode'), skylower, skyupper, skyclip, skylsigma, skyusigma : the statistics, as
+        ``sky.frame_stats``'s ``stat, lower, upper, clip, lsigma, usigma``.
+    skymethod : 'localmin' (each frame its own level) or 'globalmin' (the lowest of them for all).
+    skyuser : None, or one scalar per frame: the levels to subtract; nothing is computed then.
+    ``computed_sky`` holds the levels once they exist; they are frozen until it is assigned or a ``sky*`` keyword
+    changes.
+    ``set_config_parameters`` takes the same keywords; per-frame values are in the order of ``names``.
 
     Nothing touches the device before ``execute()``; argument errors are ValueErrors raised here."""
 
     def __init__(self, frames, maps, out_shape, names=None, weights=None, masks=None, pixfrac=1.0, kernel='square',
                  fill=0.0, cr_reject=False, rms=None, gain=None, sky=None, combine_nlow=0, combine_nhigh=0,
-                 driz_cr_snr=(3.5, 3.0), driz_cr_scale=(1.2, 0.7)):
+                 driz_cr_snr=(3.5, 3.0), driz_cr_scale=(1.2, 0.7), skysub=False, skystat='median', skymethod='localmin',
+                 skylower=None, skyupper=None, skyclip=5, skylsigma=4.0, skyusigma=4.0, skyuser=None):
         frames = list(frames)
         K = len(frames)
         if not 1 <= K <= MAX_FRAMES:
@@ -349,9 +367,16 @@ class DeviceDrizzle(object):
         self._rms_dev = {}                             # name -> the resident rms map
         self._crmask, self._merged, self._crclean = {}, {}, {}
         self._fast = False                             # execute() was called by fast_replace_image
+        self._skycfg = dict(on=False, stat='median', method='localmin', lower=None, upper=None, clip=5, lsigma=4.0,
+                            usigma=4.0, user=None)
+        self._sky = {}                                 # name -> the frozen sky value (``computed_sky``)
+        self._sky_global = None                        # 'globalmin': the lowest of the first computation
+        self._sub = {}                                 # name -> (sky value, frame - sky on the device)
         self.set_config_parameters(pixfrac=pixfrac, kernel=kernel, fill=fill, cr_reject=cr_reject, rms=rms, gain=gain,
                                    sky=sky, combine_nlow=combine_nlow, combine_nhigh=combine_nhigh,
-                                   driz_cr_snr=driz_cr_snr, driz_cr_scale=driz_cr_scale)
+                                   driz_cr_snr=driz_cr_snr, driz_cr_scale=driz_cr_scale, skysub=skysub,
+                                   skystat=skystat, skymethod=skymethod, skylower=skylower, skyupper=skyupper,
+                                   skyclip=skyclip, skylsigma=skylsigma, skyusigma=skyusigma, skyuser=skyuser)
         self._rows_host = None                         # uint8 [K][ROW_BYTES], as spx_drizzle_rows packed them
         self._rows_dev = None
         self._rows_poly = False                        # the rows are spx_drizzle_poly_rows' (a PolyMap among the maps)
@@ -382,7 +407,9 @@ class DeviceDrizzle(object):
         return np.dtype(self._dtype)
 
     def set_config_parameters(self, pixfrac=None, kernel=None, fill=None, cr_reject=None, rms=None, gain=None,
-                              sky=None, combine_nlow=None, combine_nhigh=None, driz_cr_snr=None, driz_cr_scale=None):
+                              sky=None, combine_nlow=None, combine_nhigh=None, driz_cr_snr=None, driz_cr_scale=None,
+                              skysub=None, skystat=None, skymethod=None, skylower=None, skyupper=None, skyclip=None,
+                              skylsigma=None, skyusigma=None, skyuser=None):
         if pixfrac is not None:
             pixfrac = float(pixfrac)
             if not 0.0 < pixfrac <= 1.0:
@@ -420,6 +447,11 @@ class DeviceDrizzle(object):
                 cr[key] = pair
         if cr_reject is not None:
             cr['on'] = bool(cr_reject)
+        sk = self._sky_parameters(skysub, skystat, skymethod, skylower, skyupper, skyclip, skylsigma, skyusigma,
+                                  skyuser)
+        if sk['on'] and cr['sky'] is not None:
+            raise ValueError("sky: with skysub the frames the comparison sees are sky-free (the sky's noise belongs "
+                             "in rms): give skysub or sky, not both.")
         if cr['on']:
             self._no_poly_with_cr(self._maps.values())
             if cr['rms'] is None:
@@ -431,7 +463,59 @@ class DeviceDrizzle(object):
         if rms is not None:
             self._rms_dev = {}
         self._cr = cr
+        if sk != self._skycfg:                         # a sky* keyword changed: the frozen values go
+            self._skycfg = sk
+            self._sky, self._sky_global, self._sub = {}, None, {}
         self._stale = True
+
+    def _sky_parameters(self, skysub, skystat, skymethod, skylower, skyupper, skyclip, skylsigma, skyusigma, skyuser):
+        """the ``sky*`` keywords that are given (not None) over the current ones, checked; nothing is stored"""
+        from . import sky as _sky
+        sk = dict(self._skycfg)
+        given = dict(stat=skystat, method=skymethod, lower=skylower, upper=skyupper, clip=skyclip, lsigma=skylsigma,
+                     usigma=skyusigma)
+        sk.update({k: v for k, v in given.items() if v is not None})
+        if skysub is not None:
+            sk['on'] = bool(skysub)
+        if sk['method'] not in ('localmin', 'globalmin'):
+            raise ValueError("skymethod must be 'localmin' or 'globalmin', got %r." % (sk['method'],))
+        try:
+            stat, lower, upper, clip, lsigma, usigma = _sky.check_parameters(sk['stat'], sk['lower'], sk['upper'],
+                                                                             sk['clip'], sk['lsigma'], sk['usigma'])
+        except ValueError as e:
+            raise ValueError('sky' + str(e))
+        sk.update(clip=clip, lsigma=lsigma, usigma=usigma, lower=None if lower != lower else lower,
+                  upper=None if upper != upper else upper)
+        if skyuser is not None:
+            sk['user'] = self._per_frame(skyuser, 'skyuser')
+            if not all(np.isfinite(v) for v in sk['user'].values()):
+                raise ValueError("skyuser must be finite.")
+        return sk
+
+    @property
+    def computed_sky(self):
+        """``{name: sky}`` of the frames that have a value (the reference's ``computed_sky``, resample.py:130-136):
+        computed by the first full ``execute()`` with ``skysub`` and frozen from then on.  Assigning a dict replaces
+        the values: the frames it names are subtracted by what it gives, the others get a value at the next
+        ``execute()``."""
+        return dict(self._sky)
+
+    @computed_sky.setter
+    def computed_sky(self, values):
+        new = {}
+        for n, v in dict(values).items():
+            if n not in self._pool:
+                raise ValueError("computed_sky: no frame named %r." % (n,))
+            if len(getattr(v, 'shape', ())) != 0 or not np.isfinite(float(v)):
+                raise ValueError("computed_sky: the value of frame %r must be a finite scalar." % (n,))
+            new[n] = float(v)
+        self._sky, self._sky_global, self._sub = new, None, {}
+        self._stale = True
+
+    def science(self, name):
+        """the tensor of frame ``name`` the drizzle reads: ``frame - sky`` with ``skysub``, else the frame as given"""
+        self._resident(name)
+        return self._sci(name, want=True)
 
     def _per_frame(self, value, what, maps=False):
         """{name: value} from one scalar for all frames or one entry per frame, in the order of ``names``"""
@@ -514,6 +598,8 @@ class DeviceDrizzle(object):
         c._rows_dev = None if self._rows_dev is None else self._rows_dev.clone()
         c._cr = dict(self._cr)
         c._rms_dev = dict(self._rms_dev)
+        # the sky values and the subtracted frames go along (shared tensors, own dicts)
+        c._skycfg, c._sky, c._sub = dict(self._skycfg), dict(self._sky), dict(self._sub)
         # the cosmic-ray masks and the cleaned frames go along (shared tensors, own dicts)
         c._crmask, c._merged, c._crclean = dict(self._crmask), dict(self._merged), dict(self._crclean)
         c.output_sci = c.output_wht = c.output_ctx = None
@@ -569,13 +655,58 @@ class DeviceDrizzle(object):
             f.resident = True
         return f
 
+    def _ensure_sky(self, names):
+        """A frozen sky value and the subtracted tensor for each of ``names`` that lacks one: the values of
+        ``skyuser``, else ONE statistics call over the frames without a value, each with its own mask and weight.
+        'globalmin': the lowest value of the first such call, for every frame, also for one added later.  A frame
+        without a usable pixel (it contributes nothing) gets 0.  Returns True when a tensor was made."""
+        import torch
+        from . import sky as _sky
+        sk = self._skycfg
+        todo = [n for n in names if n not in self._sky]
+        if todo and sk['user'] is not None:
+            for n in todo:
+                self._sky[n] = sk['user'][n]
+        elif todo and sk['method'] == 'globalmin' and self._sky_global is not None:
+            for n in todo:
+                self._sky[n] = self._sky_global
+        elif todo:
+            fr = [self._resident(n) for n in todo]
+            st = _sky.stats_resident([f.data for f in fr], [f.weight for f in fr], [f.mask for f in fr], self._dtype,
+                                     *_sky.check_parameters(sk['stat'], sk['lower'], sk['upper'], sk['clip'],
+                                                            sk['lsigma'], sk['usigma']))
+            vals = [float(v) if np.isfinite(v) else 0.0 for v in st.sky]
+            if sk['method'] == 'globalmin':
+                good = [float(v) for v in st.sky if np.isfinite(v)]
+                self._sky_global = min(good) if good else 0.0
+                vals = len(todo) * [self._sky_global]
+            self._sky.update(zip(todo, vals))
+        made = False
+        for n in names:
+            if n not in self._sub or self._sub[n][0] != self._sky[n]:
+                f = self._resident(n)
+                self._sub[n] = (self._sky[n], f.data - torch.tensor(self._sky[n], dtype=f.data.dtype,
+                                                                     device=f.data.device))
+                made = True
+        return made
+
+    def _sci(self, name, want=False):
+        """the tensor the rows point at: the subtracted one with ``skysub`` (made here for a listed frame, or when
+        ``want``), else the frame as given"""
+        if self._skycfg['on']:
+            if name not in self._sub and (want or self._active[name]):
+                self._ensure_sky([name])
+            if name in self._sub:
+                return self._sub[name][1]
+        return self._pool[name].data
+
     def _pack(self, names, original=False):
         """rows for ``names`` through the library's host entry (ValueError for what it refuses); with cosmic-ray
         rejection on and unless ``original``, a frame's mask is the merged one of the last full ``execute()``"""
         lib = _ffi.load()
         K = len(names)
         fr = [self._resident(n) for n in names]
-        frames = np.array([f.data.data_ptr() for f in fr], np.uint64)
+        frames = np.array([self._sci(n).data_ptr() for n in names], np.uint64)
         weights = np.array([0 if f.weight is None else f.weight.data_ptr() for f in fr], np.uint64)
         mk = [f.mask if original or not self._cr['on'] or n not in self._merged else self._merged[n]
               for n, f in zip(names, fr)]
@@ -629,6 +760,10 @@ class DeviceDrizzle(object):
         lib = _ffi.load()
         K = len(self._order)
         NY, NX = self._out_shape
+        if self._skycfg['on']:
+            listed = self.input_image_names
+            if listed and self._ensure_sky(listed):
+                self._stale = True
         if self._cr['on'] and not self._fast:
             self._reject_cosmic_rays(lib)
         elif not self._cr['on'] and self._merged:
@@ -696,7 +831,7 @@ class DeviceDrizzle(object):
             ny, nx = f.data.shape
             rs, rm = self._rms_of(name)
             gain = None if cr['gain'] is None else cr['gain'][name]
-            sky = 0.0 if cr['sky'] is None else cr['sky'][name]
+            sky = 0.0 if cr['sky'] is None else cr['sky'][name]         # with skysub: 0, the frames are sky-free
             mask = torch.empty((ny, nx), dtype=torch.uint8, device=dev)
             clean = torch.empty_like(f.data)
             _ffi.check(fn(rows.data_ptr(), K, self._order.index(name), ny, nx, med.data_ptr(), nmed.data_ptr(), NY, NX,

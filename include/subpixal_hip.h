@@ -780,8 +780,33 @@ int spx_drizzle_poly_f64(const void* rows, int nframes, int kernel, double fill,
  *   6. Mask.  crmask(i, j) = fail_2(i, j) and (some pixel of the 3 x 3 block around (i, j) has fail_1).
  *      clean(i, j) = b cast to the frame dtype where crmask is 1; elsewhere d, unchanged, NaNs included.
  *   drizzlepac's defaults: snr = (3.5, 3.0), scale = (1.2, 0.7), nlow = nhigh = 0, sky = 0, no gain.
- *   Not here: minmed and the other combine types, driz_cr_grow and the CTE tail, static masks.  The frames are taken
- *   as they are: a caller whose frames differ in sky level subtracts it first (spx_sky_stats_* below).
+ *
+ * Two or three frames (spx_drizzle_minmed_*, spx_drizzle_cr_grow_*).  With K = 2 the median is the mean and carries
+ * half of every hit, with K = 3 it carries every pixel that two frames are hit at; steps 2' and 7 are what
+ * drizzlepac answers that with (combine_type = 'minmed', combine_grow; driz_cr_grow, driz_cr_ctegrow).  They are
+ * modelled on drizzlepac, which is not in the reference tree: parity with it is UNPINNED here too, the definition is
+ * this library's own and tests/minmed_statement.py restates it in numpy.  Every decision below is float64 with
+ * contraction off and uses + - * / and comparisons only (no sqrt), so numpy reproduces it to the bit.
+ *   2'. minmed, in place of step 2.  For output pixel P with m valid s_k:
+ *      md   = step 2's value, with nlow / nhigh as given;  lo = the smallest valid s_k (0 where m = 0);
+ *      kmin = the lowest table row among the frames that supplied lo;
+ *      var  = r^2 + (g > 0 ? max((double)lo - sky, 0) / g : 0) with (r, sky, g) = row kmin of the table
+ *             (combine_rms, sky, gain) [nframes][3];
+ *      t    = (double)md - (double)lo;
+ *      hit_p = m >= 2 and t > 0 and t t > (n_p n_p) var, for (n_1, n_2) = nsigma, n_2 <= n_1;  seed = hit_1;
+ *      use_min = seed or (hit_2 and some pixel within Chebyshev distance `grow` of P, inside the grid, is a seed);
+ *      med = use_min ? lo : md;  nmed = m as before;
+ *      minmed (uint8) = 0 median, 1 minimum by the pixel's own test, 2 minimum by the neighbour rule.
+ *      grow = 0: no neighbour rule.
+ *   7. Growth of the mask, after step 6.  Seeds are step 6's crmask.  A pixel that is not a seed becomes flagged
+ *      iff it is TESTABLE in step 5's sense (inside the frame, finite, unmasked, weight > 0, valid rms, b defined)
+ *      and a seed lies in the g x g block centred on it (g odd, 1 .. 9) or at (i, j - ctedir tau) for some
+ *      tau = 1 .. c (c = ctegrow 0 .. 64, ctedir -1, 0 or +1: the readout tail runs along the frame's columns).
+ *      The grown crmask = seed or flagged.  For a newly flagged pixel clean = (T)b, the same b step 5 compares with
+ *      (the same operations in the same order); every other pixel of clean stays as step 6 left it.
+ *      g = 1 together with c = 0 or ctedir = 0: no step 7.
+ *   Not here: the other combine types, static masks.  The frames are taken as they are: a caller whose frames
+ *   differ in sky level subtracts it first (spx_sky_stats_* below).
  *
  * Both entries take the DEVICE table spx_drizzle_rows packed and only launch, as spx_drizzle_* do; neither has an
  * atomic or depends on the grid, so every output is the same bit pattern on every run.  They can be captured, with
@@ -820,6 +845,49 @@ int spx_drizzle_cr_f64(const void* rows, int nframes, int frame, int fny, int fn
                        const uint8_t* nmed, int out_ny, int out_nx, double rms_scalar, const double* rms_map,
                        double sky, double gain, double snr1, double snr2, double scale1, double scale2,
                        uint8_t* out_crmask, double* out_clean, void* stream);
+
+/*
+ * spx_drizzle_minmed_f32 / _f64 -- steps 1, 2 and 2' in two launches: the median's gather, which also writes lo and
+ * the two decision bits, and a 32 x 8 stencil pass with a halo of `grow` for the neighbour rule.  It takes the place
+ * of spx_drizzle_median_* (arguments rows .. nhigh, out_med, out_nmed and the LDS note as there; the same exception
+ * for a capture when nactive > 64).  Neither pass reads a plane it writes.
+ *   table_f64 : DEVICE float64 [nframes][3] = (combine_rms, sky, gain) per table row; a gain that is not > 0 (0, NaN):
+ *              no Poisson term.  It cannot be checked without a copy: the caller gives finite rms >= 0 and sky.
+ *   nsigma1, nsigma2 : n_1 >= n_2 >= 0;  grow : 0 .. 8
+ *   out_md, out_lo : float32 [out_ny][out_nx], step 2's median and the minimum;  out_bits : uint8, hit_1 | hit_2 << 1
+ *   out_med, out_nmed, out_minmed : the results of step 2'
+ *   SPX_E_ARG: a null pointer, nframes outside 1 .. 128, nactive outside 1 .. nframes, unknown kernel, nlow or nhigh
+ *   < 0, an nsigma that is not finite or < 0, nsigma2 > nsigma1, grow outside 0 .. 8, out_med the same plane as out_md
+ *   or out_lo, out_minmed the same as out_bits or out_nmed, out_bits the same as out_nmed.  SPX_E_SHAPE: output size as
+ *   for spx_drizzle_*.  Checked before any HIP call.
+ *
+ * spx_drizzle_cr_grow_f32 / _f64 -- step 7 for row `frame`, one launch after spx_drizzle_cr_* (arguments rows .. out_nx,
+ * rms_scalar and rms_map as there)
+ *   seed     : uint8 [ny][nx], what spx_drizzle_cr_* wrote as out_crmask
+ *   grow, ctegrow, ctedir : g odd 1 .. 9, c 0 .. 64, -1 | 0 | +1
+ *   out_crmask : uint8 [ny][nx], the grown mask; it must not be `seed`
+ *   clean    : [ny][nx] in the frame dtype, what spx_drizzle_cr_* wrote as out_clean; only newly flagged pixels are
+ *              written
+ *   SPX_E_ARG: a null pointer (rms_map may be NULL), nframes outside 1 .. 128, frame outside 0 .. nframes-1, grow even
+ *   or outside 1 .. 9, ctegrow outside 0 .. 64, ctedir outside -1 .. 1, out_crmask == seed.  SPX_E_SHAPE: as for
+ *   spx_drizzle_cr_*.  Checked before any HIP call.
+ */
+int spx_drizzle_minmed_f32(const void* rows, int nframes, int nactive, int kernel, int nlow, int nhigh,
+                           const double* table_f64, double nsigma1, double nsigma2, int grow, int out_ny, int out_nx,
+                           float* out_md, float* out_lo, uint8_t* out_bits, float* out_med, uint8_t* out_nmed,
+                           uint8_t* out_minmed, void* stream);
+int spx_drizzle_minmed_f64(const void* rows, int nframes, int nactive, int kernel, int nlow, int nhigh,
+                           const double* table_f64, double nsigma1, double nsigma2, int grow, int out_ny, int out_nx,
+                           float* out_md, float* out_lo, uint8_t* out_bits, float* out_med, uint8_t* out_nmed,
+                           uint8_t* out_minmed, void* stream);
+int spx_drizzle_cr_grow_f32(const void* rows, int nframes, int frame, int fny, int fnx, const float* med,
+                            const uint8_t* nmed, int out_ny, int out_nx, double rms_scalar, const float* rms_map,
+                            const uint8_t* seed, int grow, int ctegrow, int ctedir, uint8_t* out_crmask,
+                            float* clean, void* stream);
+int spx_drizzle_cr_grow_f64(const void* rows, int nframes, int frame, int fny, int fnx, const float* med,
+                            const uint8_t* nmed, int out_ny, int out_nx, double rms_scalar, const double* rms_map,
+                            const uint8_t* seed, int grow, int ctegrow, int ctedir, uint8_t* out_crmask,
+                            double* clean, void* stream);
 
 /*
  * Sigma-clipped statistics of WHOLE frames: the sky level that resample.DeviceDrizzle (skysub=True) subtracts from

@@ -123,6 +123,20 @@ _SIGNATURES = {
     'spx_drizzle_cr_f64': (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _vp, _vp, _c.c_int, _c.c_int,
                                       _c.c_double, _vp, _c.c_double, _c.c_double, _c.c_double, _c.c_double,
                                       _c.c_double, _c.c_double, _vp, _vp, _vp]),
+    # minmed and the mask growth.  spx_drizzle_minmed_*: device rows, nframes, nactive, kernel, nlow, nhigh, device
+    # table [K][3], nsigma1, nsigma2, grow, out_ny, out_nx, md, lo, bits, med, nmed, minmed, stream;
+    # spx_drizzle_cr_grow_*: device rows, nframes, frame, fny, fnx, med, nmed, out_ny, out_nx, rms, rms_map, seed,
+    # grow, ctegrow, ctedir, crmask, clean, stream
+    'spx_drizzle_minmed_f32': (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _vp, _c.c_double,
+                                          _c.c_double, _c.c_int, _c.c_int, _c.c_int, _vp, _vp, _vp, _vp, _vp, _vp,
+                                          _vp]),
+    'spx_drizzle_minmed_f64': (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _vp, _c.c_double,
+                                          _c.c_double, _c.c_int, _c.c_int, _c.c_int, _vp, _vp, _vp, _vp, _vp, _vp,
+                                          _vp]),
+    'spx_drizzle_cr_grow_f32': (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _vp, _vp, _c.c_int, _c.c_int,
+                                           _c.c_double, _vp, _vp, _c.c_int, _c.c_int, _c.c_int, _vp, _vp, _vp]),
+    'spx_drizzle_cr_grow_f64': (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _vp, _vp, _c.c_int, _c.c_int,
+                                           _c.c_double, _vp, _vp, _c.c_int, _c.c_int, _c.c_int, _vp, _vp, _vp]),
     # deblending of merged sources (spx_deblend_labels_*): frame, mask, filter, fky, fkx, fny, fnx, labels,
     # nlabels, boxes, connectivity, min_area, nlevels, contrast, mode, work, work_bytes, out_labels, out_parent,
     # out_dflags, max_out, out_nlabels, stream

@@ -13,6 +13,7 @@
 #include "spx_drizzle_kernels.h"
 #include "spx_drizzle_poly_kernels.h"
 #include "spx_crreject_kernels.h"
+#include "spx_minmed_kernels.h"
 #include "spx_deblend_kernels.h"
 #include "spx_background_kernels.h"
 #include "spx_sky_kernels.h"
@@ -1288,6 +1289,74 @@ int drizzle_cr(const void* rows, int nframes, int frame, int fny, int fnx, const
     SPX_HIP(hipGetLastError());
     return 0;
 }
+
+// minmed and the mask growth (spx_minmed_kernels.h)
+template <typename T>
+int drizzle_minmed(const void* rows, int nframes, int nactive, int kernel, int nlow, int nhigh, const double* table,
+                   double nsigma1, double nsigma2, int grow, int out_ny, int out_nx, float* md, float* lo,
+                   uint8_t* bits, float* med, uint8_t* nmed, uint8_t* minmed, void* stream) {
+    if (const int rc = drizzle_sizes(nframes, kernel, out_ny, out_nx)) return rc;
+    if (nactive < 1 || nactive > nframes) return fail(SPX_E_ARG, "nactive must be 1..nframes");
+    if (nlow < 0 || nhigh < 0) return fail(SPX_E_ARG, "nlow and nhigh must not be negative");
+    if (!cr_level_ok(nsigma1) || !cr_level_ok(nsigma2))
+        return fail(SPX_E_ARG, "nsigma must be finite and not negative");
+    if (nsigma2 > nsigma1) return fail(SPX_E_ARG, "the second test must not be the stricter one: nsigma2 <= nsigma1");
+    if (grow < 0 || grow > spx::kMmMaxGrow) return fail(SPX_E_ARG, "grow must be 0..8");
+    if (!rows || !table || !md || !lo || !bits || !med || !nmed || !minmed) return fail(SPX_E_ARG, "null pointer");
+    if (med == md || med == lo || minmed == bits || minmed == nmed || bits == nmed)
+        return fail(SPX_E_ARG, "the planes of the two passes must be distinct: no pass reads a plane it writes");
+    if (nlow > spx::kDrzMaxFrames) nlow = spx::kDrzMaxFrames;
+    if (nhigh > spx::kDrzMaxFrames) nhigh = spx::kDrzMaxFrames;
+    const int lds = (int)spx::drizzle_median_lds_bytes(nactive);
+    auto kern = spx::drizzle_minmed_kernel<T>;
+    if (lds > 64 * 1024) {
+        int dev = 0;
+        SPX_HIP(hipGetDevice(&dev));
+        std::lock_guard<std::mutex> lk(g_crr_mu);
+        const auto key = std::make_pair(dev, reinterpret_cast<const void*>(kern));
+        if (!g_crr_lds_ok.count(key)) {
+            SPX_HIP(hipFuncSetAttribute(key.second, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        (int)spx::drizzle_median_lds_bytes(spx::kDrzMaxFrames)));
+            g_crr_lds_ok.insert(key);
+        }
+    }
+    const int64_t tiles = (int64_t)((out_nx + spx::kDrzTileW - 1) / spx::kDrzTileW) *
+                          ((out_ny + spx::kDrzTileH - 1) / spx::kDrzTileH);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(kern, dim3(capped_grid(tiles, 1 << 20)), dim3(256), lds, s,
+                       static_cast<const spx::DrizzleRow*>(rows), nframes, nactive, kernel, nlow, nhigh, table, nsigma1,
+                       nsigma2, out_ny, out_nx, md, lo, bits, nmed);
+    SPX_HIP(hipGetLastError());
+    hipLaunchKernelGGL(spx::minmed_grow_kernel, dim3(capped_grid(tiles, 1 << 20)), dim3(256), spx::kMmGrowLdsBytes, s,
+                       md, lo, bits, grow, out_ny, out_nx, med, minmed);
+    SPX_HIP(hipGetLastError());
+    return 0;
+}
+
+template <typename T>
+int drizzle_cr_grow(const void* rows, int nframes, int frame, int fny, int fnx, const float* med, const uint8_t* nmed,
+                    int out_ny, int out_nx, double rms_scalar, const T* rms_map, const uint8_t* seed, int grow,
+                    int ctegrow, int ctedir, uint8_t* crmask, T* clean, void* stream) {
+    if (const int rc = drizzle_sizes(nframes, 0, out_ny, out_nx)) return rc;
+    if (frame < 0 || frame >= nframes) return fail(SPX_E_ARG, "frame must be a row of the table, 0..nframes-1");
+    if (grow < 1 || grow > 2 * spx::kCrGrowMaxHalf + 1 || !(grow & 1)) return fail(SPX_E_ARG, "grow must be odd, 1..9");
+    if (ctegrow < 0 || ctegrow > spx::kCrGrowMaxCte) return fail(SPX_E_ARG, "ctegrow must be 0..64");
+    if (ctedir < -1 || ctedir > 1) return fail(SPX_E_ARG, "ctedir must be -1, 0 or +1");
+    if (!rows || !med || !nmed || !seed || !crmask || !clean) return fail(SPX_E_ARG, "null pointer");
+    if (seed == crmask) return fail(SPX_E_ARG, "the seed mask and the grown mask must be distinct planes");
+    if (fny < 1 || fnx < 1 || (int64_t)fny * fnx >= 2147483647LL)
+        return fail(SPX_E_SHAPE, "the frame must hold 1 .. 2^31 - 2 pixels");
+    if (out_ny < spx::kCrMinOut || out_nx < spx::kCrMinOut)
+        return fail(SPX_E_SHAPE, "the blot's quintic needs a median of 6 x 6 pixels at least");
+    const int64_t tiles = (int64_t)((fnx + spx::kDrzTileW - 1) / spx::kDrzTileW) *
+                          ((fny + spx::kDrzTileH - 1) / spx::kDrzTileH);
+    hipLaunchKernelGGL(spx::drizzle_cr_grow_kernel<T>, dim3(capped_grid(tiles, 1 << 20)), dim3(256),
+                       spx::kCrGrowLdsBytes, reinterpret_cast<hipStream_t>(stream),
+                       static_cast<const spx::DrizzleRow*>(rows), frame, med, nmed, out_ny, out_nx, rms_scalar, rms_map,
+                       seed, grow, ctegrow, ctedir, crmask, clean);
+    SPX_HIP(hipGetLastError());
+    return 0;
+}
 }  // namespace
 
 extern "C" {
@@ -1388,6 +1457,34 @@ int spx_drizzle_cr_f64(const void* rows, int nframes, int frame, int fny, int fn
                        uint8_t* out_crmask, double* out_clean, void* stream) {
     return drizzle_cr<double>(rows, nframes, frame, fny, fnx, med, nmed, out_ny, out_nx, rms_scalar, rms_map, sky, gain,
                               snr1, snr2, scale1, scale2, out_crmask, out_clean, stream);
+}
+int spx_drizzle_minmed_f32(const void* rows, int nframes, int nactive, int kernel, int nlow, int nhigh,
+                           const double* table_f64, double nsigma1, double nsigma2, int grow, int out_ny, int out_nx,
+                           float* out_md, float* out_lo, uint8_t* out_bits, float* out_med, uint8_t* out_nmed,
+                           uint8_t* out_minmed, void* stream) {
+    return drizzle_minmed<float>(rows, nframes, nactive, kernel, nlow, nhigh, table_f64, nsigma1, nsigma2, grow, out_ny,
+                                 out_nx, out_md, out_lo, out_bits, out_med, out_nmed, out_minmed, stream);
+}
+int spx_drizzle_minmed_f64(const void* rows, int nframes, int nactive, int kernel, int nlow, int nhigh,
+                           const double* table_f64, double nsigma1, double nsigma2, int grow, int out_ny, int out_nx,
+                           float* out_md, float* out_lo, uint8_t* out_bits, float* out_med, uint8_t* out_nmed,
+                           uint8_t* out_minmed, void* stream) {
+    return drizzle_minmed<double>(rows, nframes, nactive, kernel, nlow, nhigh, table_f64, nsigma1, nsigma2, grow, out_ny,
+                                  out_nx, out_md, out_lo, out_bits, out_med, out_nmed, out_minmed, stream);
+}
+int spx_drizzle_cr_grow_f32(const void* rows, int nframes, int frame, int fny, int fnx, const float* med,
+                            const uint8_t* nmed, int out_ny, int out_nx, double rms_scalar, const float* rms_map,
+                            const uint8_t* seed, int grow, int ctegrow, int ctedir, uint8_t* out_crmask,
+                            float* clean, void* stream) {
+    return drizzle_cr_grow<float>(rows, nframes, frame, fny, fnx, med, nmed, out_ny, out_nx, rms_scalar, rms_map, seed,
+                                  grow, ctegrow, ctedir, out_crmask, clean, stream);
+}
+int spx_drizzle_cr_grow_f64(const void* rows, int nframes, int frame, int fny, int fnx, const float* med,
+                            const uint8_t* nmed, int out_ny, int out_nx, double rms_scalar, const double* rms_map,
+                            const uint8_t* seed, int grow, int ctegrow, int ctedir, uint8_t* out_crmask,
+                            double* clean, void* stream) {
+    return drizzle_cr_grow<double>(rows, nframes, frame, fny, fnx, med, nmed, out_ny, out_nx, rms_scalar, rms_map, seed,
+                                   grow, ctegrow, ctedir, out_crmask, clean, stream);
 }
 int spx_measure_errors_f32(const float* frame, const uint8_t* bad_mask, double bkg_scalar, const float* bkg_map,
                            double rms_scalar, const float* rms_map, double gain, const int32_t* labels, int fny,

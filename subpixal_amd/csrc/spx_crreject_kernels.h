@@ -133,6 +133,27 @@ SPX_DEVICE bool cr_fails(double d, float b, float D, double rms, const CrParams&
     return t > scale * (double)D + snr * sqrt(var);
 }
 
+// step 3 at ONE position (i, j) of row r's frame (inside it or not): b and whether it is defined; b = 0 where it is
+// not.  drizzle_cr_kernel's phase A and the grow pass of spx_minmed_kernels.h share it, so that the b a grown pixel
+// gets is the b the comparison saw: the same operations in the same order.
+SPX_DEVICE bool cr_blot_at(const DrizzleRow& r, const float* __restrict__ med, const uint8_t* __restrict__ nmed,
+                           int out_ny, int out_nx, int i, int j, float& b) {
+#pragma clang fp contract(off)
+    const double X = (r.a[0] * (double)i + r.a[1] * (double)j) + r.a[2];
+    const double Y = (r.a[3] * (double)i + r.a[4] * (double)j) + r.a[5];
+    bool def = X >= 0.0 && X <= (double)(out_nx - 1) && Y >= 0.0 && Y <= (double)(out_ny - 1);
+    b = 0.0f;
+    if (def) {
+        const int ix = (int)X, iy = (int)Y;
+        const int xa = ix - 2 < 0 ? 0 : ix - 2, xb = ix + 3 > out_nx - 1 ? out_nx - 1 : ix + 3;
+        const int ya = iy - 2 < 0 ? 0 : iy - 2, yb = iy + 3 > out_ny - 1 ? out_ny - 1 : iy + 3;
+        for (int y = ya; y <= yb; ++y)
+            for (int x = xa; x <= xb; ++x) def = def && nmed[(int64_t)y * out_nx + x] != 0;
+        if (def) b = blot_resample(med, out_ny, out_nx, X, Y);
+    }
+    return def;
+}
+
 template <typename T>
 SPX_TKERNEL(256)
 void drizzle_cr_kernel(const DrizzleRow* __restrict__ rows, int frame, const float* __restrict__ med,
@@ -157,19 +178,8 @@ void drizzle_cr_kernel(const DrizzleRow* __restrict__ rows, int frame, const flo
         const int i0 = (int)(tile % tiles_x) * kDrzTileW, j0 = (int)(tile / tiles_x) * kDrzTileH;
         // phase A: the blot
         for (int p = tid; p < kCrBN; p += 256) {
-            const int i = i0 - 2 + p % kCrBW, j = j0 - 2 + p / kCrBW;
-            const double X = (r.a[0] * (double)i + r.a[1] * (double)j) + r.a[2];
-            const double Y = (r.a[3] * (double)i + r.a[4] * (double)j) + r.a[5];
-            bool def = X >= 0.0 && X <= (double)(out_nx - 1) && Y >= 0.0 && Y <= (double)(out_ny - 1);
-            float b = 0.0f;
-            if (def) {
-                const int ix = (int)X, iy = (int)Y;
-                const int xa = ix - 2 < 0 ? 0 : ix - 2, xb = ix + 3 > out_nx - 1 ? out_nx - 1 : ix + 3;
-                const int ya = iy - 2 < 0 ? 0 : iy - 2, yb = iy + 3 > out_ny - 1 ? out_ny - 1 : iy + 3;
-                for (int y = ya; y <= yb; ++y)
-                    for (int x = xa; x <= xb; ++x) def = def && nmed[(int64_t)y * out_nx + x] != 0;
-                if (def) b = blot_resample(med, out_ny, out_nx, X, Y);
-            }
+            float b;
+            const bool def = cr_blot_at(r, med, nmed, out_ny, out_nx, i0 - 2 + p % kCrBW, j0 - 2 + p / kCrBW, b);
             s_b[p] = b;
             s_bdef[p] = def ? 1 : 0;
         }

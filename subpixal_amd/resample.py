@@ -31,8 +31,16 @@ the steps of the reference's full ``execute()`` (resample.py:366-390) on the dev
 drizzles (``spx_drizzle_median_*``), per frame the blot of that median, its derivative and the two-threshold
 comparison (``spx_drizzle_cr_*``), then the final drizzle with every frame's mask merged with its cosmic-ray mask.
 The definition is again the library's own, modelled on drizzlepac's createMedian / ablot / quickDeriv / drizCR and
-written out in include/subpixal_hip.h; parity with drizzlepac is UNPINNED.  ``minmed`` and the other combine types,
-``driz_cr_grow``, the CTE tail and static masks are not here.
+written out in include/subpixal_hip.h; parity with drizzlepac is UNPINNED.
+
+A visit of two or three exposures is what the median cannot clean: with K = 2 it is the mean, carries half of every
+hit and makes the comparison flag the clean frame as well.  ``combine_type='minmed'`` (``spx_drizzle_minmed_*``, step
+2' of the header) takes the minimum of the single-frame drizzles where the median stands ``combine_nsigma`` of the
+minimum's own noise above it, and around such pixels (``combine_grow``); ``driz_cr_grow`` and ``driz_cr_ctegrow`` /
+``driz_cr_ctedir`` (``spx_drizzle_cr_grow_*``, step 7) grow every frame's mask by a block and along the readout
+direction, so that a hit's faint wings do not stay in ``crclean``.  Modelled on drizzlepac's keywords of the same
+names, the definition the library's own, parity UNPINNED.  With every one of these keywords at its default
+``execute()`` makes exactly the calls it made without them.  The other combine types and static masks are not here.
 
 The per-frame table the kernel reads lives on the device; ``set_map`` and dropping or adding a frame rewrite one
 row.  Dropping only clears the frame's ``active`` flag, so the result is bit-identical to a fresh drizzle of the
@@ -303,6 +311,15 @@ class DeviceDrizzle(object):
     combine_nlow, combine_nhigh : values dropped from the median at either end where that leaves one.
     driz_cr_snr, driz_cr_scale : the two thresholds, ``(3.5, 3.0)`` and ``(1.2, 0.7)``; the second pair must not exceed
         the first.
+    combine_type : 'median' (default) or 'minmed'.  combine_nsigma : minmed's two thresholds, ``(4.0, 3.0)``.
+    combine_grow : 0 .. 8, the reach of minmed's neighbour rule (default 1).
+    combine_rms : minmed's noise of a single-frame drizzle, a scalar or one per frame; default: the frame's ``rms``
+        where that is a scalar.
+    driz_cr_grow : odd, 1 .. 9: every rejected pixel flags the testable pixels of the block around it (default 1:
+        none).  driz_cr_ctegrow : 0 .. 64, and driz_cr_ctedir, a scalar or one per frame, each -1, 0 or +1: the
+        pixels ``(i, j + ctedir tau)``, tau = 1 .. ctegrow, behind a rejected pixel ``(i, j)`` are flagged too.
+        ``crmask(name)`` is the grown mask, ``crseed(name)`` the mask before the growth; ``output_minmed`` (uint8: 0
+        median, 1 minimum, 2 minimum by the neighbour rule) is None unless minmed ran.
     skysub : subtract each frame's sky level before everything else (default False).  With it ``sky`` must stay None.
     skystat ('median' | 'mean' | 'mode'), skylower, skyupper, skyclip, skylsigma, skyusigma : the statistics, as
         ``sky.frame_stats``'s ``stat, lower, upper, clip, lsigma, usigma``.
@@ -317,7 +334,9 @@ class DeviceDrizzle(object):
     def __init__(self, frames, maps, out_shape, names=None, weights=None, masks=None, pixfrac=1.0, kernel='square',
                  fill=0.0, cr_reject=False, rms=None, gain=None, sky=None, combine_nlow=0, combine_nhigh=0,
                  driz_cr_snr=(3.5, 3.0), driz_cr_scale=(1.2, 0.7), skysub=False, skystat='median', skymethod='localmin',
-                 skylower=None, skyupper=None, skyclip=5, skylsigma=4.0, skyusigma=4.0, skyuser=None):
+                 skylower=None, skyupper=None, skyclip=5, skylsigma=4.0, skyusigma=4.0, skyuser=None,
+                 combine_type='median', combine_nsigma=(4.0, 3.0), combine_grow=1, combine_rms=None, driz_cr_grow=1,
+                 driz_cr_ctegrow=0, driz_cr_ctedir=0):
         frames = list(frames)
         K = len(frames)
         if not 1 <= K <= MAX_FRAMES:
@@ -363,9 +382,12 @@ class DeviceDrizzle(object):
         self._active = {n: True for n in names}
         self._pixfrac, self._kernel, self._fill = 1.0, 'square', 0.0
         self._names0 = list(names)                     # the order per-frame configuration values are given in
-        self._cr = dict(on=False, rms=None, gain=None, sky=None, nlow=0, nhigh=0, snr=(3.5, 3.0), scale=(1.2, 0.7))
+        self._cr = dict(on=False, rms=None, gain=None, sky=None, nlow=0, nhigh=0, snr=(3.5, 3.0), scale=(1.2, 0.7),
+                        combine='median', nsigma=(4.0, 3.0), combine_grow=1, combine_rms=None, grow=1, ctegrow=0,
+                        ctedir={n: 0 for n in names})
         self._rms_dev = {}                             # name -> the resident rms map
         self._crmask, self._merged, self._crclean = {}, {}, {}
+        self._crseed = {}                              # name -> the mask before step 7 grew it
         self._fast = False                             # execute() was called by fast_replace_image
         self._skycfg = dict(on=False, stat='median', method='localmin', lower=None, upper=None, clip=5, lsigma=4.0,
                             usigma=4.0, user=None)
@@ -376,13 +398,17 @@ class DeviceDrizzle(object):
                                    sky=sky, combine_nlow=combine_nlow, combine_nhigh=combine_nhigh,
                                    driz_cr_snr=driz_cr_snr, driz_cr_scale=driz_cr_scale, skysub=skysub,
                                    skystat=skystat, skymethod=skymethod, skylower=skylower, skyupper=skyupper,
-                                   skyclip=skyclip, skylsigma=skylsigma, skyusigma=skyusigma, skyuser=skyuser)
+                                   skyclip=skyclip, skylsigma=skylsigma, skyusigma=skyusigma, skyuser=skyuser,
+                                   combine_type=combine_type, combine_nsigma=combine_nsigma, combine_grow=combine_grow,
+                                   combine_rms=combine_rms, driz_cr_grow=driz_cr_grow, driz_cr_ctegrow=driz_cr_ctegrow,
+                                   driz_cr_ctedir=driz_cr_ctedir)
         self._rows_host = None                         # uint8 [K][ROW_BYTES], as spx_drizzle_rows packed them
         self._rows_dev = None
         self._rows_poly = False                        # the rows are spx_drizzle_poly_rows' (a PolyMap among the maps)
         self._stale = True                             # the whole table must be packed again
         self.output_sci = self.output_wht = self.output_ctx = None
         self.output_median = self.output_nmedian = self.output_crmask = self.output_crclean = None
+        self.output_minmed = None
 
     # ------------------------------------------------------------------------------------------------------
     # the reference's Resample interface
@@ -409,7 +435,9 @@ class DeviceDrizzle(object):
     def set_config_parameters(self, pixfrac=None, kernel=None, fill=None, cr_reject=None, rms=None, gain=None,
                               sky=None, combine_nlow=None, combine_nhigh=None, driz_cr_snr=None, driz_cr_scale=None,
                               skysub=None, skystat=None, skymethod=None, skylower=None, skyupper=None, skyclip=None,
-                              skylsigma=None, skyusigma=None, skyuser=None):
+                              skylsigma=None, skyusigma=None, skyuser=None, combine_type=None, combine_nsigma=None,
+                              combine_grow=None, combine_rms=None, driz_cr_grow=None, driz_cr_ctegrow=None,
+                              driz_cr_ctedir=None):
         if pixfrac is not None:
             pixfrac = float(pixfrac)
             if not 0.0 < pixfrac <= 1.0:
@@ -445,6 +473,8 @@ class DeviceDrizzle(object):
                     raise ValueError("driz_cr_%s must be two finite numbers >= 0, the second not above the first, "
                                      "got %r." % (key, val))
                 cr[key] = pair
+        self._minmed_parameters(cr, combine_type, combine_nsigma, combine_grow, combine_rms, driz_cr_grow,
+                                driz_cr_ctegrow, driz_cr_ctedir)
         if cr_reject is not None:
             cr['on'] = bool(cr_reject)
         sk = self._sky_parameters(skysub, skystat, skymethod, skylower, skyupper, skyclip, skylsigma, skyusigma,
@@ -458,6 +488,11 @@ class DeviceDrizzle(object):
                 raise ValueError("rms: cr_reject needs the frames' noise (a scalar, or per frame a scalar or a map).")
             if min(self._out_shape) < 6:
                 raise ValueError("out_shape: cr_reject needs an output of 6 x 6 pixels at least (the blot's quintic).")
+            if cr['combine'] == 'minmed' and cr['combine_rms'] is None:
+                for n in self._names0:
+                    if not isinstance(cr['rms'][n], float):
+                        raise ValueError("combine_rms: 'minmed' needs one noise value per frame, and the rms of frame "
+                                         "%r is a map: give combine_rms (a scalar, or one scalar per frame)." % (n,))
         if fill is not None:
             self._fill = fill
         if rms is not None:
@@ -467,6 +502,54 @@ class DeviceDrizzle(object):
             self._skycfg = sk
             self._sky, self._sky_global, self._sub = {}, None, {}
         self._stale = True
+
+    def _minmed_parameters(self, cr, combine_type, combine_nsigma, combine_grow, combine_rms, driz_cr_grow,
+                           driz_cr_ctegrow, driz_cr_ctedir):
+        """the minmed and growth keywords that are given (not None), checked, into the dict ``cr``"""
+        if combine_type is not None:
+            if combine_type not in ('median', 'minmed'):
+                raise ValueError("combine_type must be 'median' or 'minmed', got %r." % (combine_type,))
+            cr['combine'] = combine_type
+        if combine_nsigma is not None:
+            try:
+                pair = tuple(float(v) for v in combine_nsigma)
+            except TypeError:
+                pair = ()
+            if len(pair) != 2 or not all(np.isfinite(v) and v >= 0 for v in pair) or pair[1] > pair[0]:
+                raise ValueError("combine_nsigma must be two finite numbers >= 0, the second not above the first, "
+                                 "got %r." % (combine_nsigma,))
+            cr['nsigma'] = pair
+        for key, val, lo, hi, odd in (('combine_grow', combine_grow, 0, 8, False), ('grow', driz_cr_grow, 1, 9, True),
+                                      ('ctegrow', driz_cr_ctegrow, 0, 64, False)):
+            if val is not None:
+                name = key if key == 'combine_grow' else 'driz_cr_' + key
+                if len(getattr(val, 'shape', ())) != 0 or isinstance(val, (list, tuple)) or int(val) != val \
+                        or not lo <= val <= hi or (odd and int(val) % 2 == 0):
+                    raise ValueError("%s must be an%s integer %d .. %d, got %r." % (name, ' odd' if odd else '', lo, hi,
+                                                                                   val))
+                cr[key] = int(val)
+        if combine_rms is not None:
+            r = self._per_frame(combine_rms, 'combine_rms')
+            if not all(np.isfinite(v) and v >= 0 for v in r.values()):
+                raise ValueError("combine_rms must be finite and >= 0.")
+            cr['combine_rms'] = r
+        if driz_cr_ctedir is not None:
+            r = self._per_frame(driz_cr_ctedir, 'driz_cr_ctedir')
+            if not all(v in (-1.0, 0.0, 1.0) for v in r.values()):
+                raise ValueError("driz_cr_ctedir: each entry must be -1, 0 or +1, got %r." % (driz_cr_ctedir,))
+            cr['ctedir'] = {n: int(v) for n, v in r.items()}
+
+    def _grows(self, name):
+        """whether step 7 does anything for frame ``name``"""
+        cr = self._cr
+        return cr['grow'] > 1 or (cr['ctegrow'] > 0 and cr['ctedir'].get(name, 0) != 0)
+
+    def _cr_entries(self):
+        """the library entries a full ``execute()`` calls between its two drizzles, in order (without the dtype
+        suffix): with every minmed and growth keyword at its default, the two it always called"""
+        first = 'spx_drizzle_minmed' if self._cr['combine'] == 'minmed' else 'spx_drizzle_median'
+        grows = any(self._grows(n) for n in self.input_image_names)
+        return (first, 'spx_drizzle_cr') + (('spx_drizzle_cr_grow',) if grows else ())
 
     def _sky_parameters(self, skysub, skystat, skymethod, skylower, skyupper, skyclip, skylsigma, skyusigma, skyuser):
         """the ``sky*`` keywords that are given (not None) over the current ones, checked; nothing is stored"""
@@ -543,6 +626,11 @@ class DeviceDrizzle(object):
         or None"""
         return self._crmask.get(name)
 
+    def crseed(self, name):
+        """the mask of frame ``name`` before ``driz_cr_grow`` / ``driz_cr_ctegrow`` grew it (``crmask(name)`` itself
+        where nothing grew it), or None"""
+        return self._crseed.get(name)
+
     def crclean(self, name):
         """frame ``name`` with its rejected pixels replaced by the blotted median (the reference's ``crclean_image``),
         or None when the last full ``execute()`` made none"""
@@ -602,6 +690,7 @@ class DeviceDrizzle(object):
         c._skycfg, c._sky, c._sub = dict(self._skycfg), dict(self._sky), dict(self._sub)
         # the cosmic-ray masks and the cleaned frames go along (shared tensors, own dicts)
         c._crmask, c._merged, c._crclean = dict(self._crmask), dict(self._merged), dict(self._crclean)
+        c._crseed = dict(self._crseed)
         c.output_sci = c.output_wht = c.output_ctx = None
         return c
 
@@ -768,6 +857,7 @@ class DeviceDrizzle(object):
             self._reject_cosmic_rays(lib)
         elif not self._cr['on'] and self._merged:
             self._crmask, self._merged, self._crclean = {}, {}, {}
+            self._crseed = {}
             self._stale = True
         if self._stale or self._rows_dev is None or self._rows_poly != self._poly():
             self._rows_host = self._pack(self._order)
@@ -811,8 +901,9 @@ class DeviceDrizzle(object):
         f32 = self._dtype == 'float32'
         active = self.input_image_names
         self._crmask, self._merged, self._crclean = {}, {}, {}
+        self._crseed = {}
         if not active:
-            self.output_median = self.output_nmedian = None
+            self.output_median = self.output_nmedian = self.output_minmed = None
             self.output_crmask, self.output_crclean = [], []
             self._stale = True
             return
@@ -821,10 +912,29 @@ class DeviceDrizzle(object):
         dev, stream = rows.device, device.stream_ptr()
         med = torch.empty((NY, NX), dtype=torch.float32, device=dev)
         nmed = torch.empty((NY, NX), dtype=torch.uint8, device=dev)
-        fn = lib.spx_drizzle_median_f32 if f32 else lib.spx_drizzle_median_f64
-        _ffi.check(fn(rows.data_ptr(), K, len(active), KERNELS[self._kernel], cr['nlow'], cr['nhigh'], NY, NX,
-                      med.data_ptr(), nmed.data_ptr(), stream))
+        minmed = None
+        if cr['combine'] == 'minmed':
+            # step 2': the table (combine_rms, sky, gain) per row, the median, the minimum and the decision bits in
+            # planes of their own (no pass reads a plane it writes), then the neighbour rule
+            table = np.zeros((K, 3))
+            for k, name in enumerate(self._order):
+                r = cr['combine_rms'][name] if cr['combine_rms'] is not None else cr['rms'][name]
+                g = None if cr['gain'] is None else cr['gain'][name]
+                table[k] = (r, 0.0 if cr['sky'] is None else cr['sky'][name],
+                            g if g is not None and np.isfinite(g) and g > 0 else 0.0)
+            table = torch.from_numpy(table).cuda()
+            md, lo = torch.empty_like(med), torch.empty_like(med)
+            bits, minmed = torch.empty_like(nmed), torch.empty_like(nmed)
+            fn = lib.spx_drizzle_minmed_f32 if f32 else lib.spx_drizzle_minmed_f64
+            _ffi.check(fn(rows.data_ptr(), K, len(active), KERNELS[self._kernel], cr['nlow'], cr['nhigh'],
+                          table.data_ptr(), cr['nsigma'][0], cr['nsigma'][1], cr['combine_grow'], NY, NX, md.data_ptr(),
+                          lo.data_ptr(), bits.data_ptr(), med.data_ptr(), nmed.data_ptr(), minmed.data_ptr(), stream))
+        else:
+            fn = lib.spx_drizzle_median_f32 if f32 else lib.spx_drizzle_median_f64
+            _ffi.check(fn(rows.data_ptr(), K, len(active), KERNELS[self._kernel], cr['nlow'], cr['nhigh'], NY, NX,
+                          med.data_ptr(), nmed.data_ptr(), stream))
         fn = lib.spx_drizzle_cr_f32 if f32 else lib.spx_drizzle_cr_f64
+        fn_grow = lib.spx_drizzle_cr_grow_f32 if f32 else lib.spx_drizzle_cr_grow_f64
         host = host.copy()
         for name in active:
             f = self._pool[name]
@@ -838,10 +948,19 @@ class DeviceDrizzle(object):
                           rs, None if rm is None else rm.data_ptr(), sky, float('nan') if gain is None else gain,
                           cr['snr'][0], cr['snr'][1], cr['scale'][0], cr['scale'][1], mask.data_ptr(),
                           clean.data_ptr(), stream))
+            self._crseed[name] = mask
+            if self._grows(name):
+                # step 7 reads the seed mask and writes the grown one into a plane of its own
+                grown = torch.empty_like(mask)
+                _ffi.check(fn_grow(rows.data_ptr(), K, self._order.index(name), ny, nx, med.data_ptr(),
+                                   nmed.data_ptr(), NY, NX, rs, None if rm is None else rm.data_ptr(),
+                                   mask.data_ptr(), cr['grow'], cr['ctegrow'], cr['ctedir'].get(name, 0),
+                                   grown.data_ptr(), clean.data_ptr(), stream))
+                mask = grown
             self._crmask[name], self._crclean[name] = mask, clean
             self._merged[name] = mask if f.mask is None else (f.mask | mask)
             host[self._order.index(name), _ROW_MASK:_ROW_MASK + 8].view(np.uint64)[0] = self._merged[name].data_ptr()
-        self.output_median, self.output_nmedian = med, nmed
+        self.output_median, self.output_nmedian, self.output_minmed = med, nmed, minmed
         self.output_crmask = [self._crmask[n] for n in active]
         self.output_crclean = [self._crclean[n] for n in active]
         self._rows_host, self._rows_dev = host, torch.from_numpy(host).cuda()
